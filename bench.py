@@ -16,7 +16,14 @@ processes itself (torch.distributed.run as a child process, before this process
 touches the GPU) and exits with their status; under torch.distributed.run the
 world size must equal N.
 
-Prints ONE JSON line on rank 0 with the contract fields plus
+A plain run sets up, warms up, times the steps, writes `--dump-outputs DIR`
+(DIR/frame.npy: the frame the last timed step left, float32) and prints the line
+with its headline fields; everything below that takes passes or CPU time of its
+own -- the single-layer passes, the counting and performed-work passes behind the
+roofline, the parity rows against the oracle, the CPU baseline -- runs only with
+`--full`, and is null in a plain run's line.
+
+Prints ONE JSON line on rank 0 with the contract fields plus (`--full`)
   "roofline"      the dominant kernel (the trace kind with the most standalone
                   time per pass: the shadow-ray trace on the sponza stand-in since
                   the camera-ray cull of build 15) against the ceiling that binds
@@ -55,6 +62,25 @@ SALU_PEAK_GIPS = 256 * CLK_GHZ
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+def use_writable_scene_dir():
+    """The generated scenes (.obj / .mtl / .rtc, chiaroscuro_amd.scenes) go under the package's build/
+    directory; where this user may not write there (a tree built by another user, a read-only checkout)
+    they go to a per-user directory under the system's temporary directory instead, named through
+    CHIARO_SCENE_DIR so that every rank of a multi-GPU run uses the same one."""
+    if os.environ.get("CHIARO_SCENE_DIR"):
+        return
+    p = ROOT / "chiaroscuro-raytracer_amd" / "build" / "scenes"
+    while not p.exists():
+        p = p.parent
+    if os.access(p, os.W_OK | os.X_OK):
+        return
+    import tempfile
+    alt = Path(tempfile.gettempdir()) / ("chiaroscuro_scenes_%d" % os.getuid())
+    alt.mkdir(mode=0o700, parents=True, exist_ok=True)
+    os.environ["CHIARO_SCENE_DIR"] = str(alt)
+    log("bench: %s is not writable, scenes go to %s" % (p, alt))
 
 
 def physical_cores():
@@ -135,6 +161,25 @@ def parity_rows(yres, nrows):
     if nrows <= 1:
         return [yres // 2]
     return sorted({int(round(i * (yres - 1) / (nrows - 1))) for i in range(nrows)})
+
+
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(directory, frame):
+    """--dump-outputs: the accumulated frame [yres][xres][3] the last timed step left (layers 1 .. warmup +
+    steps blended, what a caller of the timed path holds) as DIR/frame.npy, float32.  A frame over 64 MB
+    (the 4K configuration) is cut to a fixed, seeded sample of whole rows in ascending order: the same rows
+    for every run at that frame size."""
+    import numpy as np
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    f = np.ascontiguousarray(frame, np.float32)
+    if f.nbytes > DUMP_MAX_BYTES:
+        nrows = DUMP_MAX_BYTES // f[0].nbytes
+        rows = np.sort(np.random.default_rng(0xC41A05C0).choice(f.shape[0], nrows, replace=False))
+        f = np.ascontiguousarray(f[rows])
+    np.save(d / "frame.npy", f)
 
 
 def frame_parity(osc, frame_rows, rows, cam, xres, yres, spp, k, seed, nlayers):
@@ -444,6 +489,13 @@ def main():
     ap.add_argument("--parity-rows", type=int, default=8,
                     help="rank 0 checks this many rows of the timed frame (every layer, full spp) bit for bit "
                          "against the oracle after the timed region (0: skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: the single-layer "
+                         "passes, the counting and performed-work passes (roofline), the parity rows and the CPU "
+                         "baseline; without it those fields of the line are null")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes the frame the timed steps left (what a caller of the timed path receives) "
+                         "to DIR/frame.npy, float32")
     args = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if "WORLD_SIZE" not in os.environ and (args.gpus or 1) > 1:
@@ -482,6 +534,7 @@ def run_rank(args, world, backend):
             log("bench: world size %d, backend %s, %s, collective timeout %.0f s" %
                 (dist.get_world_size(), dist.get_backend(), ver, args.dist_timeout))
 
+    use_writable_scene_dir()
     rtc = scenes.config_rtc(args.config)
     t0 = time.time()
     scene = ca.Scene(rtc, *(("xres", args.res.split("x")[0], "yres", args.res.split("x")[1]) if args.res else ()))
@@ -585,17 +638,19 @@ def run_rank(args, world, backend):
     timed_build = dev.last_trace_build() if hasattr(dev, "last_trace_build") else None
     nlayers_done = layer - 1  # the frame holds layers 1 .. nlayers_done (warmup and timed groups)
     # rows of the timed frame for the parity check (rank 0; the oracle runs after the collectives)
-    prows = parity_rows(yres, args.parity_rows) if args.parity_rows > 0 else []
+    prows = parity_rows(yres, args.parity_rows) if (args.full and args.parity_rows > 0) else []
     frame_rows = fr.frame[prows].cpu().numpy() if (prows and fr.frame is not None) else None
     if args.save_frame and fr.frame is not None:
         import numpy as np
         np.save(args.save_frame, fr.frame.cpu().numpy())
+    if args.dump_outputs and fr.frame is not None:
+        dump_outputs(args.dump_outputs, fr.frame.cpu().numpy())
     # the reference's unit of work, untimed by the line's value: one rayTrace call = ONE layer per
     # render pass (main.cpp:16, the preview's R key) -- a warmup pass, then --single-layer-steps passes
     # of the next layers (the frame's rows above are already taken), each bracketed like the steps
     single_ms = None
     single_rays = 0.0
-    if args.single_layer_steps > 0:
+    if args.full and args.single_layer_steps > 0:
         times = []
         srays = []
         for j in range(args.single_layer_steps + 1):
@@ -629,42 +684,45 @@ def run_rank(args, world, backend):
     single_rays_all = float(sum(r[4] for r in per_rank))  # one layer's rays over every rank's tiles
     rank_render_ms = [round(r[1], 3) for r in per_rank]
 
-    # counting pass (untimed): algorithmic bytes of one launch of this rank
-    if watch:
-        watch.phase = "counting and performed-work passes"
-    dev.set_option("counters", 1)
-    pc = ca.render_params(xres, yres, spp, k, seed, layer=first_timed, rank=rank, nranks=world, tile=tile)
-    scratch = torch.zeros((yres, xres, 3), dtype=torch.float32, device=backend.device)
-    if world == 1:
-        dev.render_device(cam, pc, scratch.data_ptr(), stream)
-    else:
-        scratch_tiles = torch.zeros((fr.layout.max_tiles, tile, tile, 3), dtype=torch.float32, device=backend.device)
-        dev.render_tiles_device(cam, pc, scratch_tiles.data_ptr(), stream)
-    cc = dev.counters()
-    cts = dev.trace_stats() if wavefront else None
-    totals["bytes"] = ca.algorithmic_bytes(cc, cc["pixels"])
-    totals["tritest"] = cc["tritest"]
-    totals["texhit"] = cc["texhit"]
-    totals["count_rays"] = cc["closest"] + cc["shadow"]
-    dev.set_option("counters", 0)
-    # performed-work pass (untimed): the default trace build's kernels with counters of what they
-    # actually execute and load (cr_get_perf), the same layer
+    # counting pass (--full, untimed): algorithmic bytes of one launch of this rank
     perf = None
-    if wavefront and args.variant in (-1, 18, 26, 40, 42, 43, 44, 49, 53, 54, 59) and hasattr(dev, "perf") and not args.no_perf_pass:
-        dev.set_option("perf_counters", 1)
+    if args.full:
+        if watch:
+            watch.phase = "counting and performed-work passes"
+        dev.set_option("counters", 1)
+        pc = ca.render_params(xres, yres, spp, k, seed, layer=first_timed, rank=rank, nranks=world, tile=tile)
+        scratch = torch.zeros((yres, xres, 3), dtype=torch.float32, device=backend.device)
         if world == 1:
             dev.render_device(cam, pc, scratch.data_ptr(), stream)
         else:
+            scratch_tiles = torch.zeros((fr.layout.max_tiles, tile, tile, 3), dtype=torch.float32, device=backend.device)
             dev.render_tiles_device(cam, pc, scratch_tiles.data_ptr(), stream)
-        perf = dev.perf()
-        dev.set_option("perf_counters", 0)
+        cc = dev.counters()
+        cts = dev.trace_stats() if wavefront else None
+        totals["bytes"] = ca.algorithmic_bytes(cc, cc["pixels"])
+        totals["tritest"] = cc["tritest"]
+        totals["texhit"] = cc["texhit"]
+        totals["count_rays"] = cc["closest"] + cc["shadow"]
+        dev.set_option("counters", 0)
+        # performed-work pass (untimed): the default trace build's kernels with counters of what they
+        # actually execute and load (cr_get_perf), the same layer
+        if wavefront and args.variant in (-1, 18, 26, 40, 42, 43, 44, 49, 53, 54, 59) and hasattr(dev, "perf") and not args.no_perf_pass:
+            dev.set_option("perf_counters", 1)
+            if world == 1:
+                dev.render_device(cam, pc, scratch.data_ptr(), stream)
+            else:
+                dev.render_tiles_device(cam, pc, scratch_tiles.data_ptr(), stream)
+            perf = dev.perf()
+            dev.set_option("perf_counters", 0)
 
     out = None
+    roofline = cpu = parity = None  # (a plain run: only --full measures them)
     if rank == 0:
         value = rays_all / elapsed / 1e6
         # the queries actually traversed: value less the zero-contribution NEE queries answered without
         # a trace (rayTracer.cpp:104 issues every one; SURVEY §8d counts them, the line says how many)
         value_traced = (rays_all - nee_all) / elapsed / 1e6
+    if rank == 0 and args.full:
         kms = totals["kernel_ms"] / max(totals["launches"], 1)
         pass_bytes = totals["bytes"]  # counting pass: one render pass, same size as a timed one
         pass_gbs = pass_bytes / (kms / 1e3) / 1e9 if kms > 0 else 0.0
@@ -783,6 +841,8 @@ def run_rank(args, world, backend):
                         "frac": round(ach / HBM_PEAK_GBS, 5), "traffic": pass_view["traffic"],
                         "kernel": pass_view["kernels"], "kernel_ms": round(kms, 3),
                         "algorithmic_bytes_per_launch": int(pass_bytes)}
+    if rank == 0:
+        counted = "count_rays" in totals  # (the counting pass ran: --full)
         label = {"sponza": "sponza_standin (Sponza-Crytek stand-in, ~261k tris) 1920x1080",
                  "sponza_4k": "sponza_standin (Sponza-Crytek stand-in) 3840x2160",
                  "nanobox": "nanobox_standin (textured nanosuit-in-a-box stand-in, ~19k tris, the asset's 21 MB texture set) 1920x1080",
@@ -794,6 +854,7 @@ def run_rank(args, world, backend):
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": bool(args.full),
             "ms_per_step": round(elapsed / args.steps * 1e3, 3),
             # the same layer as ONE render pass (the reference's unit of work: one rayTrace call), wall
             # time per pass after the timed region; value and ms_per_step time the pass groups
@@ -815,10 +876,12 @@ def run_rank(args, world, backend):
                        "rays_answered_untraced": int(nee_all),
                        "rank_render_ms": rank_render_ms, "layers_per_pass": nl_pass,
                        "pass_groups": [list(g) for g in groups], "trace_build": timed_build,
-                       "mean_tritest_per_ray": round(totals["tritest"] / max(totals["count_rays"], 1), 2),
+                       "mean_tritest_per_ray": round(totals["tritest"] / max(totals["count_rays"], 1), 2)
+                       if counted else None,
                        # textured hits of one layer (counting pass; 3 texel bytes each in SURVEY §8d's bytes)
                        # and the scene's texture bytes (src/mesh.cpp:21-35 reads them)
-                       "texhit_per_layer": int(totals["texhit"]), "texhit_bytes_per_layer": 3 * int(totals["texhit"]),
+                       "texhit_per_layer": int(totals["texhit"]) if counted else None,
+                       "texhit_bytes_per_layer": 3 * int(totals["texhit"]) if counted else None,
                        "texture_bytes": int(tex_bytes)},
             "roofline": roofline,
             "cpu_baseline": cpu,

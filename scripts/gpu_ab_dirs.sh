@@ -9,7 +9,7 @@ DIRS=(); while [ $# -gt 0 ] && [ "$1" != "--" ]; do DIRS+=("$1"); shift; done
 for r in 1 2; do
   for L in "${DIRS[@]}"; do
     if [ $L = tree ]; then unset CHIARO_LIB_DIR; else export CHIARO_LIB_DIR=$GRAFT_REPO_ROOT/$L; fi
-    timeout -k 10 300 python -u bench.py --no-cpu-baseline --parity-rows 0 --single-layer-steps 0 --steps 20 --warmup 5 \
+    timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --parity-rows 0 --single-layer-steps 0 --steps 20 --warmup 5 \
         "$@" > gpurun_out/abd.json 2> gpurun_out/abd.err || { tail -5 gpurun_out/abd.err; exit 1; }
     python -c "
 import json; d=json.load(open('gpurun_out/abd.json')); r=d['roofline']

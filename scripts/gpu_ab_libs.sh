@@ -8,7 +8,7 @@ for r in 1 2; do
   for O in "$@"; do
     for L in base new; do
       if [ $L = base ]; then export CHIARO_LIB_DIR=$GRAFT_REPO_ROOT/ab_base; else unset CHIARO_LIB_DIR; fi
-      timeout -k 10 300 python -u bench.py --no-cpu-baseline --parity-rows 0 --single-layer-steps 0 --steps 20 --warmup 5 \
+      timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --parity-rows 0 --single-layer-steps 0 --steps 20 --warmup 5 \
           $O > gpurun_out/abl.json 2> gpurun_out/abl.err || { tail -5 gpurun_out/abl.err; exit 1; }
       python -c "
 import json; d=json.load(open('gpurun_out/abl.json')); r=d['roofline']

@@ -22,6 +22,6 @@ python scripts/pass_breakdown.py $(find gpurun_out/prof_$TAG/trace -name "*kerne
 timeout -k 10 300 python scripts/rank_time.py --nranks 1,2,4,8 --rounds 2 > profiles/${TAG}_rank_time.txt 2> gpurun_out/rank_time.err || { echo "rank_time failed"; exit 1; }
 cat profiles/${TAG}_rank_time.txt
 # the bench line with this run's PMC summaries (traffic, issue)
-timeout -k 10 600 python bench.py > profiles/${TAG}_bench_default.json 2> gpurun_out/bench_default.log || { echo "bench failed"; tail -20 gpurun_out/bench_default.log; exit 1; }
+timeout -k 10 600 python bench.py --full > profiles/${TAG}_bench_default.json || { echo "bench failed"; exit 1; }
 cat profiles/${TAG}_bench_default.json
 cp -r profiles/. gpurun_out/profiles/

@@ -12,7 +12,7 @@ python scripts/prof_summary.py gpurun_out/prof_${TAG}_$CFG ${TAG}_$CFG --config 
 rm -rf gpurun_out/pmc_issue
 bash scripts/pmc_issue.sh --config $CFG --steps 16 --warmup 0 --no-cpu-baseline || exit 1
 python scripts/pmc_issue_summary.py gpurun_out/pmc_issue/a/pmc_counter_collection.csv profiles/pmc_issue_$CFG.json $SPP || exit 1
-timeout -k 10 600 python bench.py --config $CFG --steps 16 --warmup 1 > profiles/${TAG}_bench_$CFG.json 2> gpurun_out/bench_$CFG.log || { echo "bench $CFG failed"; tail -20 gpurun_out/bench_$CFG.log; exit 1; }
+timeout -k 10 600 python bench.py --full --config $CFG --steps 16 --warmup 1 > profiles/${TAG}_bench_$CFG.json || { echo "bench $CFG failed"; exit 1; }
 cat profiles/${TAG}_bench_$CFG.json
 cp -r profiles/. gpurun_out/profiles/
 # the raw rocprofv3 csvs stay on the box (their summaries are in profiles/): gpurun returns at most 64 MiB

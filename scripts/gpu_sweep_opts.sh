@@ -14,7 +14,7 @@ i=0
 for r in $(seq $N); do
   for O in "$@"; do
     i=$((i+1))
-    timeout -k 10 300 python -u bench.py --no-cpu-baseline --parity-rows 2 --single-layer-steps 0 --steps 20 --warmup 5 \
+    timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --parity-rows 2 --single-layer-steps 0 --steps 20 --warmup 5 \
         $BA $O > gpurun_out/sw_$i.json 2> gpurun_out/sw_$i.err || { tail -5 gpurun_out/sw_$i.err; exit 1; }
     python -c "
 import json; d=json.load(open('gpurun_out/sw_$i.json')); r=d['roofline']

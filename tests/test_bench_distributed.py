@@ -32,7 +32,7 @@ def test_bench_two_ranks_gloo(tmp_path, ca, po, scenes):
         env.pop(k, None)
     cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", str(STEPS), "--warmup", str(WARMUP),
            "--config", "cornell", "--res", "%dx%d" % RES, "--spp", str(SPP), "--no-cpu-baseline", "--layers-per-pass", "2",
-           "--save-frame", str(frame)]
+           "--save-frame", str(frame), "--full", "--dump-outputs", str(tmp_path / "dump")]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -57,6 +57,10 @@ def test_bench_two_ranks_gloo(tmp_path, ca, po, scenes):
     assert line["config"]["rays"] == rays
     got = np.load(frame)
     assert got.shape == ref.shape and (got.view(np.uint32) == ref.view(np.uint32)).all() and got.mean() > 0
+    # --dump-outputs: the frame the last timed step left (the single-layer passes of --full come after it)
+    dumped = np.load(tmp_path / "dump" / "frame.npy")
+    assert dumped.dtype == np.float32 and (dumped.view(np.uint32) == ref.view(np.uint32)).all()
+    assert line["full"] is True
     assert line["single_layer_ms"] > 0  # one-layer passes after the timed groups (not in value)
     # the bench's own parity check of the timed frame: every row it sampled, every layer, bit for bit
     par = line["parity"]
@@ -64,6 +68,52 @@ def test_bench_two_ranks_gloo(tmp_path, ca, po, scenes):
     assert par["values"] == len(par["rows"]) * RES[0] * 3 and par["rows"][0] == 0 and par["rows"][-1] == RES[1] - 1
     # value: the rays of all ranks over the slowest rank's wall time (ms_per_step is that / steps)
     want = rays / (line["ms_per_step"] * STEPS / 1e3) / 1e6
+    assert abs(line["value"] - want) <= 1e-3 * want + 2e-3
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_timed_frame(tmp_path, ca, po, scenes):
+    """A plain run (no --full), two ranks over gloo: every rank renders the warmup layer and the --steps timed
+    layers and nothing else (the stand-in device logs every pass it renders), the line keeps its headline
+    fields with ms_per_step the timed wall time over --steps, what only --full measures is null, and
+    --dump-outputs leaves the frame after the last timed step: the oracle's progressive render of layers
+    1 .. warmup + steps, bit for bit."""
+    res, spp, warmup, steps = (40, 24), 2, 1, 3
+    logs = tmp_path / "plans"
+    logs.mkdir()
+    env = dict(os.environ, CHIARO_BENCH_BACKEND="%s:make" % (ROOT / "tests" / "bench_cpu_backend.py"),
+               MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="2", CHIARO_QUIET="1", CHIARO_TEST_PLAN_LOG=str(logs))
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
+        env.pop(k, None)
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", str(steps), "--warmup", str(warmup),
+           "--config", "cornell", "--res", "%dx%d" % res, "--spp", str(spp), "--layers-per-pass", "2",
+           "--dump-outputs", str(tmp_path / "dump")]
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert [p.name for p in (tmp_path / "dump").iterdir()] == ["frame.npy"]
+    got = np.load(tmp_path / "dump" / "frame.npy")
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["n_gpus"] == 2 and line["steps"] == steps and line["warmup"] == warmup and line["full"] is False
+    assert line["unit"] == "Mray/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["config"]["pass_groups"] == [[2, 1], [1, 1]]
+    for key in ("roofline", "cpu_baseline", "vs_cpu", "parity", "single_layer_ms", "single_layer_mray_s"):
+        assert line[key] is None, key
+    # every pass a rank rendered: the warmup layer and the timed groups, no counting or single-layer pass
+    for q in range(2):
+        assert (logs / ("rank%d.txt" % q)).read_text().split("\n") == ["1 1", "2 2", "4 1", ""]
+    sc = ca.Scene(scenes.config_rtc("cornell"), "xres", str(res[0]), "yres", str(res[1]))
+    i = sc.info
+    m = ca.Model(sc)
+    osc = po.OracleScene(m.triangles(), leaf_size=i["leaf_size"], textures=m.textures())
+    cam = ca.camera(i["VP"], i["LA"], i["UP"], i["yview"], res[0], res[1]).as_array()
+    ref, rays = None, 0
+    for L in range(1, warmup + steps + 1):
+        ref, c = osc.render(cam, res[0], res[1], spp, i["k"], i["seed"], layer=L, bg=i["background"], pixels=ref)
+        if L > warmup:
+            rays += c["closest"] + c["shadow"]
+    assert got.dtype == np.float32 and got.shape == ref.shape
+    assert (got.view(np.uint32) == ref.view(np.uint32)).all() and got.mean() > 0
+    assert line["config"]["rays"] == rays
+    want = rays / (line["ms_per_step"] * steps / 1e3) / 1e6
     assert abs(line["value"] - want) <= 1e-3 * want + 2e-3
 
 
@@ -86,7 +136,7 @@ def test_bench_ranks_gloo_ragged_uneven_plans(tmp_path, nranks, ca, po, scenes):
         env.pop(k, None)
     cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", str(nranks), "--steps", str(steps), "--warmup",
            str(warmup), "--config", "cornell", "--res", "%dx%d" % res, "--spp", str(spp), "--no-cpu-baseline",
-           "--layers-per-pass", "4", "--parity-rows", "4", "--save-frame", str(frame)]
+           "--layers-per-pass", "4", "--parity-rows", "4", "--save-frame", str(frame), "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

@@ -22,7 +22,7 @@ ROOT = Path(__file__).resolve().parents[1]
 
 @pytest.mark.parametrize("config", ["cornell", "cornell_box", "nanobox", "sponza", "sponza_4k"])
 def test_bench_config_full_size_rows_bitexact(config):
-    cmd = [sys.executable, "-u", str(ROOT / "bench.py"), "--config", config, "--steps", "2", "--warmup", "0",
+    cmd = [sys.executable, "-u", str(ROOT / "bench.py"), "--config", config, "--steps", "2", "--warmup", "0", "--full",
            "--parity-rows", "3", "--no-cpu-baseline", "--no-perf-pass", "--single-layer-steps", "0"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
