@@ -273,6 +273,25 @@ struct WfArgs {
     // counted as a shadow query (option "wf_nee_skip")
     int nee_skip;
 };
+// The wavefront kernels take (RenderArgs A, WfArgs W, uint32_t g) by value, and the kernel-argument segment
+// holds the three one after another, each at its own alignment.  The trace kernels read the arguments they
+// need once per query from the segment at these offsets (wavefront.hip kargs_w) instead of holding them
+// in registers across the traversal; tests/test_trace_args.py compares the offsets and sizes with the
+// built code object's argument metadata.
+constexpr size_t karg_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+enum : uint32_t {
+    KARG_A = 0u,
+    KARG_W = (uint32_t)karg_align_up(sizeof(RenderArgs), alignof(WfArgs)),
+    KARG_G = (uint32_t)karg_align_up(KARG_W + sizeof(WfArgs), alignof(uint32_t)),
+};
+struct WfKernArgs { // (the same layout as a struct: members in order, each at its alignment)
+    RenderArgs A;
+    WfArgs W;
+    uint32_t g;
+};
+static_assert(sizeof(RenderArgs) % alignof(RenderArgs) == 0 && alignof(RenderArgs) <= 16 && alignof(WfArgs) <= 16,
+              "kernel-argument layout");
+static_assert(offsetof(WfKernArgs, W) == KARG_W && offsetof(WfKernArgs, g) == KARG_G, "kernel-argument layout");
 // rays 2x2 float4, hits 2, shadow ray 2, exclude + occ 8 B, state, (direct, w) pairs, 2 x 2 sort keys + perms,
 // camera sample position, resolve mark
 // spare: + 21 for the queue arrays' spare slots of chunked appends, P / 8 of them at 168 B (cabi.cpp spare_for)

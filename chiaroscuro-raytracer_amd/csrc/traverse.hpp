@@ -342,6 +342,10 @@ struct TraceDefaults {
     static constexpr bool DEAD = false;   // shadow queues with dead entries (wf_shade's chunked appends) skipped
     static constexpr bool LX = false;     // a divergent leaf's masked tests spread over the wave (leaf_exchange)
     static constexpr bool LXD = false;    // LX builds: the exchange's prefix by a DPP scan
+    // the options every real run leaves at their defaults fixed at compile time: WfArgs::vis_mark 1,
+    // WfArgs::ended_only 0 (no overlapped tail), RenderArgs::lc_debug 0 -- the launchers take such an
+    // instantiation only for a launch whose options have these values (wavefront.hip tc::Fixed)
+    static constexpr bool FIX = false;
 };
 
 // A lane's deferred leaf (LX builds): the references of the leaf whose first record is `first` that its

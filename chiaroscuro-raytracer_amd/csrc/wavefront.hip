@@ -277,8 +277,10 @@ enum : uint32_t { SHADOW_VIS = 0u, SHADOW_OCC = 1u };
 // With WfArgs::vis_mark idx is the path | ENDED_BIT when it ends at this bounce: a visible answer sets the
 // visible bit of the path's resolve mark (one byte), an occluded one writes nothing.
 enum : uint32_t { ENDED_BIT = 0x80000000u };
+// FIX: vis_mark is 1 for this instantiation (TraceDefaults::FIX)
+template <bool FIX>
 __device__ __forceinline__ void shadow_store(const WfArgs &W, uint32_t g, uint32_t idx, bool occluded) {
-    if (W.vis_mark) {
+    if (FIX || W.vis_mark) {
         if (!occluded) W.mark[idx & ~ENDED_BIT] = (uint8_t)((g << 2) | 2u | (idx >> 31));
     } else if (W.vis_dw) {
         ((uint32_t *)(W.dw + (size_t)(2 * (g - 1)) * W.P + idx))[3] = occluded ? SHADOW_OCC : SHADOW_VIS;
@@ -315,9 +317,32 @@ __device__ __forceinline__ bool nee_visible(const WfArgs &W, uint32_t slot) {
 // CULL (camera instantiation only): triangle tests skipped by the screen-space cull
 // boxes (camcull.hpp, A.cull); the lane keeps its sample's screen position.
 // C: the build's configuration (traverse.hpp TraceDefaults; the builds: namespace tc below)
+//
+// The refill and the answer store run once per query, the traversal between them once per step: what only
+// those two read -- the queues, their counters and order, the result arrays, the generation -- is loaded
+// from the kernel-argument segment (kernels.hpp KARG_*) where it is used, so it holds no scalar register
+// (or spill lane of a VGPR) across trav_round / leaf_exchange.  kargs_here: the segment's address made
+// opaque to the compiler at this point, so the loads stay scalar loads from the constant address space
+// and stay here instead of moving to the kernel's entry.
+typedef const __attribute__((address_space(4))) char *kargs_ptr;
+__device__ __forceinline__ kargs_ptr kargs_here() {
+    kargs_ptr p = (kargs_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return p;
+}
+// (a copy the compiler splits into its fields: only those the caller reads are loaded)
+__device__ __forceinline__ WfArgs kargs_w(kargs_ptr p) {
+    WfArgs w;
+    __builtin_memcpy(&w, p + KARG_W, sizeof(WfArgs));
+    return w;
+}
+__device__ __forceinline__ uint32_t kargs_g(kargs_ptr p) {
+    return *(const __attribute__((address_space(4))) uint32_t *)(p + KARG_G);
+}
+
 template <class C>
 __global__ void __launch_bounds__(256, C::MINW) wf_trace(RenderArgs A, WfArgs W, uint32_t g) {
-    static constexpr bool SHADOW = C::SHADOW, FULL = C::FULL, CAM = C::CAM, PC = C::PC;
+    static constexpr bool SHADOW = C::SHADOW, FULL = C::FULL, CAM = C::CAM, PC = C::PC, FIX = C::FIX;
     static constexpr int CULL = C::CULL;
     static_assert(!CULL || (CAM && !SHADOW), "the cull applies to camera rays");
     extern __shared__ uint2 ring_lds[];
@@ -325,8 +350,6 @@ __global__ void __launch_bounds__(256, C::MINW) wf_trace(RenderArgs A, WfArgs W,
     const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t n = SHADOW ? *cnt_shadow(W, g) : *cnt_closest(W, g);
-    uint32_t *work = SHADOW ? work_shadow(W, g) : work_closest(W, g);
-    const float4 *rays = SHADOW ? W.sray : W.ray[g & 1];
     Ctr c = {};
     Diag dg = {};
     dg.on = FULL && ((A.diag_kinds >> (SHADOW ? TK_SHADOW : (CAM ? TK_CAMERA : TK_CLOSEST))) & 1u);
@@ -344,6 +367,15 @@ __global__ void __launch_bounds__(256, C::MINW) wf_trace(RenderArgs A, WfArgs W,
     for (;;) {
         const uint64_t need_m = __ballot(state == ST_NEED_WORK), busy_m = __ballot(state == busy_st);
         if (need_m && (busy_m == 0 || (uint32_t)__popcll(need_m) >= refill)) {
+            // (this block's W and g: the kernel's arguments read here, see kargs_here)
+            const kargs_ptr ka = kargs_here();
+            const WfArgs W = kargs_w(ka);
+            const uint32_t g = kargs_g(ka);
+            uint32_t *work = SHADOW ? work_shadow(W, g) : work_closest(W, g);
+            // (selects, not W.ray[g & 1]: an indexed read would keep the whole copy of W in scratch)
+            const float4 *rays = SHADOW ? W.sray : (g & 1u) ? W.ray[1] : W.ray[0];
+            uint4 *hits = (g & 1u) ? W.hit[1] : W.hit[0];
+            const bool vis_mark = FIX || W.vis_mark, ended_only = !FIX && W.ended_only;
             const bool xp = (W.xcd >> (SHADOW ? 0 : (g == 1 ? 2 : 1))) & 1u;
             uint32_t *xwork = W.cnt + WF_XBASE + ((SHADOW ? WF_G : 0u) + g) * WF_XCDS * WF_XSTRIDE;
             for (;;) { // refill; a ray culled by the root box is answered at once and refetched
@@ -375,14 +407,14 @@ __global__ void __launch_bounds__(256, C::MINW) wf_trace(RenderArgs A, WfArgs W,
                         const float4 r0 = rays[2 * (size_t)idx], r1 = rays[2 * (size_t)idx + 1];
                         // overlapped tail: a path that continues traces this ray in wf_tail (the lane
                         // stays idle and takes another; no `continue`: every lane reaches the count below)
-                        if (!(SHADOW && W.ended_only && (W.sexcl[idx] & SEXCL_CONT))) {
+                        if (!(SHADOW && ended_only && (W.sexcl[idx] & SEXCL_CONT))) {
                         o = ld3(r0);
                         d = ld3(r1);
                         const uint32_t sx = SHADOW ? W.sexcl[idx] : 0u;
                         if (SHADOW) exclude = sx & ~SEXCL_CONT;
                         // the result goes to path idx's dw record (vis_dw) or resolve mark (vis_mark: its
                         // ended bit rides in idx)
-                        if (SHADOW && W.vis_mark) idx = __float_as_uint(r0.w) | ((sx & SEXCL_CONT) ? 0u : ENDED_BIT);
+                        if (SHADOW && vis_mark) idx = __float_as_uint(r0.w) | ((sx & SEXCL_CONT) ? 0u : ENDED_BIT);
                         else if (SHADOW && W.vis_dw) idx = __float_as_uint(r0.w);
                         if (CULL) { // ray idx of generation 1 is path idx's camera ray
                             const float2 q = W.cxy[idx];
@@ -392,16 +424,16 @@ __global__ void __launch_bounds__(256, C::MINW) wf_trace(RenderArgs A, WfArgs W,
                         // a dead camera ray or a dead queue entry (wf_shade's chunked appends): no query -- for
                         // shadow queues only in the C::DEAD builds (the check costs the others registers)
                         if ((!SHADOW || C::DEAD) && __float_as_uint(r0.w) == NO_PATH) {
-                            if (!SHADOW) W.hit[g & 1][idx] = make_uint4(0u, 0u, 0u, 0u);
+                            if (!SHADOW) hits[idx] = make_uint4(0u, 0u, 0u, 0u);
                         } else if (iss = true, trav_begin(S, o, d, SHADOW, r1.w, T)) {
                             state = busy_st;
                             if (FULL) diag_begin(&dg);
                         } else if (SHADOW) {
-                            if (PC) pc.vb += W.vis_mark ? 1u : 4u;
-                            shadow_store(W, g, idx, false); // culled: visible (kdtree.cpp:285-287)
+                            if (PC) pc.vb += vis_mark ? 1u : 4u;
+                            shadow_store<FIX>(W, g, idx, false); // culled: visible (kdtree.cpp:285-287)
                         } else {
                             if (PC) pc.vb += 16;
-                            W.hit[g & 1][idx] = make_uint4(0u, 0u, 0u, 0u);
+                            hits[idx] = make_uint4(0u, 0u, 0u, 0u);
                         }
                         }
                     }
@@ -415,18 +447,21 @@ __global__ void __launch_bounds__(256, C::MINW) wf_trace(RenderArgs A, WfArgs W,
         }
         // the query's result: the answer stored, the lane free
         auto answer = [&](uint32_t r) {
-            if (PC) pc.vb += SHADOW ? (W.vis_mark ? (r == ST_OCCLUDED ? 0u : 1u) : 4u) : 16u;
-            if (SHADOW) shadow_store(W, g, idx, r == ST_OCCLUDED);
+            const kargs_ptr ka = kargs_here(); // (the result arrays: read here, as the refill's arguments)
+            const WfArgs W = kargs_w(ka);
+            const uint32_t g = kargs_g(ka);
+            if (PC) pc.vb += SHADOW ? ((FIX || W.vis_mark) ? (r == ST_OCCLUDED ? 0u : 1u) : 4u) : 16u;
+            if (SHADOW) shadow_store<FIX>(W, g, idx, r == ST_OCCLUDED);
             // w: the hit's leaf + 1, the queue sort's key region
-            else W.hit[g & 1][idx] = r == ST_HIT ? make_uint4(__float_as_uint(d.z), __float_as_uint(d.x),
+            else ((g & 1u) ? W.hit[1] : W.hit[0])[idx] = r == ST_HIT ? make_uint4(__float_as_uint(d.z), __float_as_uint(d.x),
                                                        __float_as_uint(d.y), T.node + 1u)
                                           : make_uint4(0u, 0u, 0u, 0u);
             state = ST_NEED_WORK;
         };
         if (!C::LX) {
             if (state == busy_st) {
-                const uint32_t r = trav_round<C>(A.lc_debug, A.lc_min, S, ring_lds, W.gstack, W.gstride, gid, o, d, SHADOW, exclude, T,
-                                                 c, csx, csy, A.cull, A.cull_node, FULL ? &dg : nullptr,
+                const uint32_t r = trav_round<C>(FIX ? 0 : A.lc_debug, A.lc_min, S, ring_lds, W.gstack, W.gstride, gid, o, d, SHADOW, exclude, T,
+                                                 c, csx, csy, CULL ? A.cull : nullptr, CULL ? A.cull_node : nullptr, FULL ? &dg : nullptr,
                                                  PC ? &pc : nullptr, A.desc_quorum);
                 if (r != busy_st) answer(r);
             }
@@ -435,9 +470,9 @@ __global__ void __launch_bounds__(256, C::MINW) wf_trace(RenderArgs A, WfArgs W,
         LeafX lx = {0u, 0u};
         uint32_t r = busy_st;
         if (state == busy_st)
-            r = trav_round<C>(A.lc_debug, A.lc_min,
-                S, ring_lds, W.gstack, W.gstride, gid, o, d, SHADOW, exclude, T, c, csx, csy, A.cull,
-                A.cull_node, FULL ? &dg : nullptr, PC ? &pc : nullptr, A.desc_quorum, &lx);
+            r = trav_round<C>(FIX ? 0 : A.lc_debug, A.lc_min,
+                S, ring_lds, W.gstack, W.gstride, gid, o, d, SHADOW, exclude, T, c, csx, csy, CULL ? A.cull : nullptr,
+                CULL ? A.cull_node : nullptr, FULL ? &dg : nullptr, PC ? &pc : nullptr, A.desc_quorum, &lx);
         // LX: the deferred leaves' tests by the whole wave (traverse.hpp leaf_exchange), then each deferred
         // lane ends its round as trav_round does after a leaf
         if (C::LX && __ballot(r == ST_LEAFX)) {
@@ -1314,7 +1349,17 @@ struct WfVariant {
     // the shadow trace of a queue wf_shade appended in chunks (its dead entries skipped); null: the build's
     // wf_shade appends per iteration
     void (*shadow_dead)(RenderArgs, WfArgs, uint32_t) = nullptr;
+    // the closest, shadow and shadow_dead traces with the default options fixed at compile time (tc::Fixed);
+    // null: the build has none, every launch takes the kernels above
+    void (*closest_fix)(RenderArgs, WfArgs, uint32_t) = nullptr;
+    void (*shadow_fix)(RenderArgs, WfArgs, uint32_t) = nullptr;
+    void (*shadow_dead_fix)(RenderArgs, WfArgs, uint32_t) = nullptr;
 };
+// True when every option a tc::Fixed instantiation fixes has its fixed value for this launch
+// (TraceDefaults::FIX); any other value selects the build's generic kernels.
+static bool wf_fixed_options(const RenderArgs &A, const WfArgs &W) {
+    return W.vis_mark == 1 && W.ended_only == 0u && A.lc_debug == 0;
+}
 
 // The trace configurations of the builds (traverse.hpp TraceDefaults), by what they restate.
 namespace tc {
@@ -1360,6 +1405,9 @@ struct Count : TraceDefaults { static constexpr bool FULL = true; static constex
 struct CameraCount : Count { static constexpr bool CAM = true; };
 struct ClosestCount : Count {};
 struct ShadowCount : Count { static constexpr bool SHADOW = true; };
+// a build's trace with the options of TraceDefaults::FIX at their defaults, fixed at compile time (the
+// default builds 59 and 44): the same build number, taken by the launchers when wf_fixed_options holds
+template <class B> struct Fixed : B { static constexpr bool FIX = true; };
 } // namespace tc
 
 // (macro arguments with commas come parenthesised: CR_UNPAREN strips the parentheses)
@@ -1397,7 +1445,8 @@ static const WfBuild kWf[] = {
     //     VGPRs): 357.5 / 355.3 vs 358.4 / 358.1 ms per pass, nanobox 162.4 vs 163.7 ms (shadow 30.7 -> 29.9)
     {43, {wf_trace_packet<8, 2, false, true>, wf_trace<tc::ClosestFatLc>, wf_trace<tc::ShadowFatLcFd>, 8, 8, 2, 1, 4}},
     {44, {wf_trace_packet<8, 2, false, true>, wf_trace<tc::ClosestFat>, wf_trace<tc::ShadowFatFd>, 8, 8, 2, 1, 0,
-          wf_trace<tc::ShadowFatFdDead>}},
+          wf_trace<tc::ShadowFatFdDead>, wf_trace<tc::Fixed<tc::ClosestFat>>, wf_trace<tc::Fixed<tc::ShadowFatFd>>,
+          wf_trace<tc::Fixed<tc::ShadowFatFdDead>>}},
     // 49: 43 whose secondary closest, shadow and tail traces read the compressed leaf cull records
     //     (leafcull.hpp LC_RECC: boxes on the scene's 16-bit grid, octahedral axes, half constants)
     {49, {wf_trace_packet<8, 2, false, true>, wf_trace<tc::ClosestFatLc5>, wf_trace<tc::ShadowFatLc5Fd>, 8, 8, 2, 1, 5,
@@ -1416,7 +1465,8 @@ static const WfBuild kWf[] = {
     //     adds instead of six bit-sliced ballots with their mbcnt pairs): 2348 -> 2395 Mray/s, shadow trace
     //     38.4 -> 37.6 ms, closest 67.3 -> 65.5 ms (three interleaved rounds)
     {59, {wf_trace_packet<8, 2, false, true>, wf_trace<tc::ClosestFatLc5LxD>, wf_trace<tc::ShadowFatLc5FdLxD>, 8, 8, 2, 1, 5,
-          wf_trace<tc::ShadowFatLc5FdDeadLxD>}},
+          wf_trace<tc::ShadowFatLc5FdDeadLxD>, wf_trace<tc::Fixed<tc::ClosestFatLc5LxD>>,
+          wf_trace<tc::Fixed<tc::ShadowFatLc5FdLxD>>, wf_trace<tc::Fixed<tc::ShadowFatLc5FdDeadLxD>>}},
 };
 static const int kNumWf = (int)(sizeof(kWf) / sizeof(kWf[0]));
 // the build numbered `variant`, or null when it is not compiled in
@@ -1473,6 +1523,16 @@ int num_wf_variants() {
 // camera rays, which an eye lying exactly on a split plane breaks: build 15's then.
 static void (*camera_kernel(const WfVariant &v, const RenderArgs &A))(RenderArgs, WfArgs, uint32_t) {
     return (v.packet && A.eye_on_split) ? wf_build(15)->camera : v.camera;
+}
+// The secondary closest and the shadow trace of a launch: the build's tc::Fixed instantiation when it has
+// one and the launch's options are the fixed ones, else its generic kernel.
+static void (*closest_kernel(const WfVariant &v, const RenderArgs &A, const WfArgs &W))(RenderArgs, WfArgs, uint32_t) {
+    return v.closest_fix && wf_fixed_options(A, W) ? v.closest_fix : v.closest;
+}
+static void (*shadow_kernel(const WfVariant &v, const RenderArgs &A, const WfArgs &W,
+                            bool dead))(RenderArgs, WfArgs, uint32_t) {
+    if (dead) return v.shadow_dead_fix && wf_fixed_options(A, W) ? v.shadow_dead_fix : v.shadow_dead;
+    return v.shadow_fix && wf_fixed_options(A, W) ? v.shadow_fix : v.shadow;
 }
 // The chunk's camera rays come from the packet trace itself (WfArgs::cam_fused) when the ctx asks for it
 // (W.cam_fused on entry), the camera kernel is the packet trace, generation 1 runs as its own launches
@@ -1730,8 +1790,8 @@ int launch_wavefront_chunk(const RenderArgs &A, const WfArgs &W0, int num_cus, h
         Wc.gstack = gstack;
         const int kind = g == 1 ? TK_CAMERA : TK_CLOSEST;
         if ((err = trace_event(te, s, kind, true))) return;
-        hipLaunchKernelGGL(g == 1 ? camera_kernel(v, A) : v.closest, dim3(g == 1 ? blocks : cblocks), dim3(blk),
-                           lds, s, A, Wc, g);
+        hipLaunchKernelGGL(g == 1 ? camera_kernel(v, A) : closest_kernel(v, A, Wc), dim3(g == 1 ? blocks : cblocks),
+                           dim3(blk), lds, s, A, Wc, g);
         err = trace_event(te, s, kind, false);
     };
     W.cam_fused = camera_fuses(v, A, W) ? 1 : 0;
@@ -1780,7 +1840,7 @@ int launch_wavefront_chunk(const RenderArgs &A, const WfArgs &W0, int num_cus, h
         W.order = order_s;
         W.ended_only = overlap ? 1u : 0u;
         if ((err = trace_event(te, st, TK_SHADOW, true))) break;
-        hipLaunchKernelGGL(dead ? v.shadow_dead : v.shadow, dim3(sblocks), dim3(blk), lds, st, A, W, g);
+        hipLaunchKernelGGL(shadow_kernel(v, A, W, dead), dim3(sblocks), dim3(blk), lds, st, A, W, g);
         if ((err = trace_event(te, st, TK_SHADOW, false))) break;
         if (!(W.measure_skip & 1u)) hipLaunchKernelGGL(wf_resolve, dim3(sgrid), dim3(256), 0, st, A, W, g);
         W.ended_only = 0u;
@@ -1842,8 +1902,8 @@ int run_wavefront_lanes(const RenderArgs &A, WfLane *L, int nl, int num_cus, hip
         Wc.gstack = gstack;
         const int kind = g == 1 ? TK_CAMERA : TK_CLOSEST;
         if ((err = trace_event(te, s, kind, true))) return;
-        hipLaunchKernelGGL(g == 1 ? camera_kernel(v, A) : v.closest, dim3(g == 1 ? blocks : cblocks), dim3(blk),
-                           lds, s, A, Wc, g);
+        hipLaunchKernelGGL(g == 1 ? camera_kernel(v, A) : closest_kernel(v, A, Wc), dim3(g == 1 ? blocks : cblocks),
+                           dim3(blk), lds, s, A, Wc, g);
         err = trace_event(te, s, kind, false);
     };
     auto shade = [&](WfLane &ln, Run &r) { // wf_shade(g), then the queue lengths to the host, async
@@ -1897,9 +1957,9 @@ int run_wavefront_lanes(const RenderArgs &A, WfLane *L, int nl, int num_cus, hip
         WfArgs Ws = r.W;
         Ws.order = order_s;
         if ((err = trace_event(te, ln.st, TK_SHADOW, true))) return true;
-        hipLaunchKernelGGL(v.shadow, dim3(sblocks), dim3(blk), lds, ln.st, A, Ws, g);
+        hipLaunchKernelGGL(shadow_kernel(v, A, Ws, false), dim3(sblocks), dim3(blk), lds, ln.st, A, Ws, g);
         if ((err = trace_event(te, ln.st, TK_SHADOW, false))) return true;
-        hipLaunchKernelGGL(wf_resolve, dim3(sgrid), dim3(256), 0, ln.st, A, r.W, g);
+        if (!(r.W.measure_skip & 1u)) hipLaunchKernelGGL(wf_resolve, dim3(sgrid), dim3(256), 0, ln.st, A, r.W, g);
         if (next) {
             if ((err = (int)hipEventRecord(ln.join, ln.side)) || (err = (int)hipStreamWaitEvent(ln.st, ln.join, 0)))
                 return true;

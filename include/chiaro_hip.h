@@ -289,7 +289,11 @@ int cr_get_trace_stats(cr_ctx *ctx, cr_trace_stats *out);
  * "refill" (1..64: idle lanes of a wave that trigger a path-state step in the
  * dynamic-fetch variants), "counters" (1 = also count inner/leaf/tritest and
  * the wave_* diagnostics; 0 = only the per-query tallies, for timed launches),
- * "block", "waves_per_cu".  Returns CR_OK or CR_E_INVALID. */
+ * "block", "waves_per_cu".  Returns CR_OK or CR_E_INVALID.
+ * The default trace builds (59 / 44) run closest and shadow trace kernels with "wf_vis_mark" 1, no
+ * overlapped tail ("wf_tail_overlap" 0) and "lc_debug" 0 fixed at compile time; a non-default value of
+ * one of these selects the build's generic trace kernels for the launches it applies to (the same build
+ * number and the same results, a few percent slower). */
 int cr_set_option(cr_ctx *ctx, const char *key, int64_t value);
 /* Diagnostics of the last counting render (wavefront trace kernels, option
  * "diag_kinds" = mask of trace kinds 1 camera / 2 closest / 4 shadow): leaf-round

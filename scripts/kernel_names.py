@@ -17,7 +17,8 @@ def trace_info(name: str):
         if "wf_tail<true" in name:
             return "tail", "counting"
         return "tail", ("perf" if re.search(r"wf_tail<[^()]*, true>\(", name) else "lean")
-    m = re.search(r"wf_trace<cr::tc::(\w+)", name)
+    # (cr::tc::Fixed<C>: C with the default options fixed at compile time -- the same kind and mode)
+    m = re.search(r"wf_trace<(?:cr::tc::Fixed<)?cr::tc::(\w+)", name)
     if not m:
         return None
     t = m.group(1)
