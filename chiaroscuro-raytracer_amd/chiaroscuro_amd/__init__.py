@@ -177,7 +177,7 @@ _host = None
 # Every symbol declared in include/chiaro_hip.h and include/chiaroscuro.h.
 HIP_SYMBOLS = ("cr_create", "cr_destroy", "cr_last_error", "cr_upload_scene", "cr_render", "cr_render_device",
                "cr_render_tiles_device", "cr_blend_tiles_device", "cr_tiles_for_rank", "cr_tile_origin", "cr_intersect",
-               "cr_intersect_shadow", "cr_get_counters", "cr_last_kernel_ms", "cr_get_trace_stats", "cr_set_option", "cr_synchronize", "cr_get_diag", "cr_get_perf", "cr_trace_build_available", "cr_last_trace_build",
+               "cr_intersect_shadow", "cr_intersect_device", "cr_intersect_shadow_device", "cr_get_counters", "cr_last_kernel_ms", "cr_get_trace_stats", "cr_set_option", "cr_synchronize", "cr_get_diag", "cr_get_perf", "cr_trace_build_available", "cr_last_trace_build",
                "cr_tonemap_setup", "cr_tonemap_device", "cr_tonemap",
                "cr_comm_unique_id", "cr_comm_init", "cr_comm_destroy", "cr_render_dist_device",
                "cr_device_count", "cr_group_create", "cr_group_destroy", "cr_group_last_error", "cr_group_size", "cr_group_ok",
@@ -254,6 +254,8 @@ def libs():
                                           C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)])
     _sig(hip, "cr_intersect", C.c_int, [P, C.c_uint32, FP, FP, UP, UP, FP, FP])
     _sig(hip, "cr_intersect_shadow", C.c_int, [P, C.c_uint32, FP, FP, FP, UP, UP])
+    _sig(hip, "cr_intersect_device", C.c_int, [P, C.c_uint32, P, P, P, P, P, P, P])
+    _sig(hip, "cr_intersect_shadow_device", C.c_int, [P, C.c_uint32, P, P, P, P, P, P])
     _sig(hip, "cr_get_counters", C.c_int, [P, C.POINTER(CrCounters)])
     _sig(hip, "cr_last_kernel_ms", C.c_float, [P])
     _sig(hip, "cr_get_trace_stats", C.c_int, [P, C.POINTER(CrTraceStats)])
@@ -590,6 +592,63 @@ class Device:
         if libs()[0].cr_tile_origin(C.byref(p), int(rank), int(local), C.byref(x0), C.byref(y0)):
             raise ValueError("cr_tile_origin: no such tile")
         return x0.value, y0.value
+
+    def intersect_device(self, n: int, d_orig_ptr: int, d_dir_ptr: int, d_hit_ptr: int, d_tri_ptr: int = 0,
+                         d_bary_ptr: int = 0, d_dist_ptr: int = 0, stream: int = 0):
+        """cr_intersect_device: n closest-hit queries on device arrays ([n][3] float origins / directions,
+        [n] uint32 hit / tri, [n][2] float bary, [n] float dist; tri / bary / dist may be 0 and keep their
+        contents where a query misses), enqueued on `stream` without a host synchronisation."""
+        self._chk(libs()[0].cr_intersect_device(self._c, int(n), C.c_void_p(d_orig_ptr), C.c_void_p(d_dir_ptr),
+                                                C.c_void_p(d_hit_ptr), C.c_void_p(d_tri_ptr or None),
+                                                C.c_void_p(d_bary_ptr or None), C.c_void_p(d_dist_ptr or None),
+                                                C.c_void_p(stream)), "cr_intersect_device")
+
+    def intersect_shadow_device(self, n: int, d_orig_ptr: int, d_dir_ptr: int, d_dist_ptr: int, d_light_ptr: int,
+                                d_occluded_ptr: int, stream: int = 0):
+        """cr_intersect_shadow_device: n shadow queries on device arrays, enqueued on `stream`."""
+        self._chk(libs()[0].cr_intersect_shadow_device(self._c, int(n), C.c_void_p(d_orig_ptr), C.c_void_p(d_dir_ptr),
+                                                       C.c_void_p(d_dist_ptr), C.c_void_p(d_light_ptr),
+                                                       C.c_void_p(d_occluded_ptr), C.c_void_p(stream)),
+                  "cr_intersect_shadow_device")
+
+    def _query_tensor(self, t, dtype, shape, what):
+        import torch
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device.index == self.device and t.dtype == dtype and
+                t.is_contiguous() and tuple(t.shape) == shape):
+            raise ValueError("%s: a contiguous %s tensor of shape %s on cuda:%d is required" % (
+                what, dtype, shape, self.device))
+        return t
+
+    def intersect_tensors(self, orig, dirs) -> dict:
+        """cr_intersect_device on torch tensors: orig, dirs contiguous float32 [n, 3] on this ctx's device.
+        Runs on torch's current stream without synchronising; returns {"hit", "tri" (int32 tensors holding
+        the uint32 values), "bary", "dist"}; tri / bary / dist are zero where a query misses."""
+        import torch
+        n = int(orig.shape[0])
+        self._query_tensor(orig, torch.float32, (n, 3), "orig")
+        self._query_tensor(dirs, torch.float32, (n, 3), "dirs")
+        hit = torch.zeros(n, dtype=torch.int32, device=orig.device)
+        tri = torch.zeros(n, dtype=torch.int32, device=orig.device)
+        bary = torch.zeros((n, 2), dtype=torch.float32, device=orig.device)
+        dist = torch.zeros(n, dtype=torch.float32, device=orig.device)
+        self.intersect_device(n, orig.data_ptr(), dirs.data_ptr(), hit.data_ptr(), tri.data_ptr(),
+                              bary.data_ptr(), dist.data_ptr(), torch.cuda.current_stream(orig.device).cuda_stream)
+        return {"hit": hit, "tri": tri, "bary": bary, "dist": dist}
+
+    def intersect_shadow_tensors(self, orig, dirs, dist, light):
+        """cr_intersect_shadow_device on torch tensors: orig, dirs float32 [n, 3], dist float32 [n], light int32
+        [n] (the uint32 triangle ids' bits), contiguous, on this ctx's device.  Runs on torch's current stream
+        without synchronising; returns the occluded flags as an int32 tensor."""
+        import torch
+        n = int(orig.shape[0])
+        self._query_tensor(orig, torch.float32, (n, 3), "orig")
+        self._query_tensor(dirs, torch.float32, (n, 3), "dirs")
+        self._query_tensor(dist, torch.float32, (n,), "dist")
+        self._query_tensor(light, torch.int32, (n,), "light")
+        occ = torch.zeros(n, dtype=torch.int32, device=orig.device)
+        self.intersect_shadow_device(n, orig.data_ptr(), dirs.data_ptr(), dist.data_ptr(), light.data_ptr(),
+                                     occ.data_ptr(), torch.cuda.current_stream(orig.device).cuda_stream)
+        return occ
 
     def intersect(self, orig: np.ndarray, dirs: np.ndarray) -> dict:
         orig = np.ascontiguousarray(orig, np.float32).reshape(-1, 3)

@@ -127,6 +127,45 @@ __global__ void __launch_bounds__(128) intersect_kernel(QueryArgs Q) {
     flush_counters(Q.counters, c);
 }
 
+// intersect_kernel over an index list (cr_intersect_device's QR_LEGACY queries, queryroute.hpp): thread j
+// answers query list[j] for j < *count (list null: query j for j < Q.n) with the same traverse<>, so such
+// a query behaves exactly as cr_intersect's does.
+__global__ void __launch_bounds__(128) intersect_list_kernel(QueryArgs Q, const uint32_t *list, const uint32_t *count) {
+    extern __shared__ uint32_t lds[];
+    const uint32_t depth = Q.stack_depth;
+    Stack stk{lds, (float *)(lds + depth * blockDim.x), (float *)(lds + 2 * depth * blockDim.x), blockDim.x};
+    Ctr c = {};
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t m = list ? min(*count, Q.n) : Q.n;
+    if (j < m) {
+        const uint32_t i = list ? list[j] : j;
+        if (i < Q.n) {
+            const f3 o = mk(Q.orig[3 * (size_t)i], Q.orig[3 * (size_t)i + 1], Q.orig[3 * (size_t)i + 2]);
+            const f3 d = mk(Q.dir[3 * (size_t)i], Q.dir[3 * (size_t)i + 1], Q.dir[3 * (size_t)i + 2]);
+            uint32_t t = 0;
+            float bx = 0.f, by = 0.f, ds = 0.f;
+            if (Q.shadow) {
+                c.shadow++;
+                Q.hit[i] = traverse<true>(Q.S, stk, o, d, Q.dist[i], Q.light[i], t, bx, by, ds, c) ? 1u : 0u;
+            } else {
+                c.closest++;
+                const bool h = traverse<false>(Q.S, stk, o, d, 0.f, 0xffffffffu, t, bx, by, ds, c);
+                Q.hit[i] = h ? 1u : 0u;
+                if (h) {
+                    c.hit++;
+                    if (Q.tri) Q.tri[i] = t;
+                    if (Q.bary) {
+                        Q.bary[2 * (size_t)i] = bx;
+                        Q.bary[2 * (size_t)i + 1] = by;
+                    }
+                    if (Q.dist_out) Q.dist_out[i] = ds;
+                }
+            }
+        }
+    }
+    flush_counters(Q.counters, c);
+}
+
 // Root-side unpermute + progressive blend of gathered tile buffers.
 __global__ void __launch_bounds__(256) blend_tiles_kernel(BlendArgs B) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; // pixel in frame
@@ -181,6 +220,16 @@ int launch_intersect(const QueryArgs &Q, hipStream_t st) {
     const uint32_t grid = (Q.n + block - 1) / block;
     if (grid == 0) return 0;
     hipLaunchKernelGGL(intersect_kernel, dim3(grid), dim3(block), lds, st, Q);
+    return (int)hipGetLastError();
+}
+
+int launch_intersect_list(const QueryArgs &Q, const uint32_t *list, const uint32_t *count, hipStream_t st) {
+    const uint32_t block = 128;
+    const size_t lds = (size_t)3 * Q.stack_depth * block * sizeof(uint32_t);
+    const uint32_t grid = (uint32_t)(((uint64_t)Q.n + block - 1) / block);
+    if (grid == 0) return 0;
+    if (list && !count) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(intersect_list_kernel, dim3(grid), dim3(block), lds, st, Q, list, count);
     return (int)hipGetLastError();
 }
 

@@ -308,6 +308,8 @@ int num_wf_variants();
 uint32_t wf_shade_blocks(int num_cus, int shade_waves);
 // true when the variant's camera trace skips Moller-Trumbore tests by the cull boxes
 bool wf_variant_culls(int variant);
+// true when the variant's secondary closest and shadow traces read leaf cull records (leafcull.hpp)
+bool wf_variant_leaf_cull(int variant);
 bool wf_variant_available(int variant); // compiled in (the default compile holds builds 0, 15, 18, 26)
 bool wf_perf_available(int variant);    // a performed-work instance of this trace build exists (18, 26)
 // cull boxes of this render's camera for the nrefs leaf references (+ 4 padding boxes)
@@ -377,6 +379,48 @@ struct TonemapArgs {
 };
 
 int launch_intersect(const QueryArgs &Q, hipStream_t st);
+// intersect_kernel's queries over an index list (kernels.hip): thread j answers query list[j] of Q's arrays
+// for j < *count (list null: query j, j < Q.n); the grid covers Q.n threads.  Device arrays, stream-ordered.
+int launch_intersect_list(const QueryArgs &Q, const uint32_t *list, const uint32_t *count, hipStream_t st);
+
+// Device-resident batched ray queries (cr_intersect_device / cr_intersect_shadow_device; queries.hip,
+// DESIGN.md §3.18): one chunk of n queries.  The ingest kernel routes every query (queryroute.hpp) and
+// appends it either to the trace queue -- records {o, w = query index of the chunk}, {d, w = limit}, the
+// light to ignore and a sort key whose bit QUERY_ROUTE_BIT is set for QR_FAT queries, so the sorted order
+// is the QR_DEFAULT queries, then the QR_FAT ones -- or to the index list of the QR_LEGACY queries.
+// The finish kernel turns the append counters into the queue counts and work counters the trace launches
+// read (QUERY_G_DEFAULT / QUERY_G_FAT: the default build takes entries [0, na) of the order, the fat
+// kernels [na, na + nb)); the scatter kernel writes the traced queries' answers at their indices.
+enum : uint32_t {
+    QUERY_WORLD_BITS = 5, QUERY_DIR_RES = 16, // key: 15 bits of origin, 8 of direction
+    QUERY_ROUTE_BIT = 23, QUERY_KEY_BITS = 24, // three 8-bit digit passes
+    QUERY_G_DEFAULT = 2, QUERY_G_FAT = 4,      // generation numbers of the two trace launches (never 1)
+    QC_TRACED = 0, QC_LEGACY = 1, QC_DEFAULT = 2, QC_N = 4, // append counters
+};
+struct QueryDevArgs {
+    DevScene S;
+    uint32_t n, shadow;
+    uint32_t route;    // option "query_route": 0 automatic, 1 every query QR_LEGACY, 2 no QR_DEFAULT
+    uint32_t no_cull;  // 1: the scene's default build has no leaf cull -- QR_FAT queries join the default queue
+    uint32_t sort;     // 1: full keys; 0: the route bit alone (one stable pass keeps the append order)
+    const float *orig, *dir, *dist; // the chunk's inputs and outputs (the caller's arrays at the chunk's start)
+    const uint32_t *light;
+    uint32_t *hit, *tri;
+    float *bary, *dist_out;
+    float4 *ray;       // [2 cap]
+    uint32_t *sexcl;   // [cap]
+    uint32_t *key;     // [cap] set to ~0 before the ingest: unused slots sort last
+    uint32_t *list;    // [cap] QR_LEGACY query indices
+    uint4 *hits;       // [cap] closest results by queue slot
+    uint32_t *occ;     // [cap] shadow results by queue slot
+    uint32_t *qc;      // [QC_N] append counters, zeroed before the ingest
+    uint32_t *cnt;     // [WF_CNT] the trace kernels' counters (WfArgs::cnt)
+};
+int launch_query_ingest(const QueryDevArgs &Q, hipStream_t st); // ingest + finish
+int launch_query_scatter(const QueryDevArgs &Q, hipStream_t st);
+// wavefront.hip: one closest / shadow trace launch over a query queue
+int launch_query_trace(const RenderArgs &A, const WfArgs &W, uint32_t g, bool shadow, bool cull, int variant,
+                       int num_cus, hipStream_t st);
 int launch_blend(const BlendArgs &B, hipStream_t st);
 int launch_tonemap(const TonemapArgs &T, hipStream_t st);
 

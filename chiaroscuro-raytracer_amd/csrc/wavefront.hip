@@ -25,6 +25,7 @@
 // Queue appends are wave-aggregated (one atomic per wave, lane order kept), so
 // neighbouring paths -- samples of the same pixel -- stay neighbours in the
 // queues and the trace waves stay coherent.
+#include "append.hpp"
 #include "camcull.hpp"
 #include "traverse.hpp"
 
@@ -39,52 +40,7 @@ enum : uint32_t { NO_SLOT = 0xffffffffu, NO_PATH = 0xffffffffu, DEAD_RAY = 1u };
 // (the overlapped tail traces those; triangle ids stay below 2^31)
 enum : uint32_t { SEXCL_CONT = 0x80000000u };
 
-// Block-aggregated appends (call with the whole block, uniformly): one global atomicAdd per block and
-// queue instead of one per wave -- same-address atomics from every wave of the grid serialise in one L2
-// slice.  Slots keep lane order within a wave and wave order within the block.
-// (lds: one word per wave of the block, up to 16, then the base)
-enum : uint32_t { APP_W = 16 };
-// N appends of one block at once (wf_shade's shadow and closest queues): one barrier round and
-// the N global atomics in flight together instead of one after another.  lds: [2][4 N + N] words,
-// the half `buf` alternating between consecutive calls (so no barrier is needed before the next
-// call writes it: the one after that is separated from this one by the next call's barriers).
-template <int N>
-__device__ __forceinline__ void block_append_n(uint32_t *const (&counter)[N], const bool (&pred)[N], uint32_t *lds,
-                                               uint32_t buf, uint32_t (&slot)[N]) {
-    uint32_t *L = lds + buf * (APP_W + 1u) * N;
-    const uint32_t wave = threadIdx.x >> 6;
-    uint64_t m[N];
-#pragma unroll
-    for (int q = 0; q < N; q++) {
-        m[q] = __ballot(pred[q]);
-        if ((threadIdx.x & 63u) == 0) L[APP_W * q + wave] = (uint32_t)__popcll(m[q]);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t tot[N];
-#pragma unroll
-        for (int q = 0; q < N; q++) {
-            uint32_t s = 0;
-            for (uint32_t w = 0; w < (blockDim.x >> 6); w++) {
-                const uint32_t c = L[APP_W * q + w];
-                L[APP_W * q + w] = s;
-                s += c;
-            }
-            tot[q] = s;
-        }
-        uint32_t base[N];
-#pragma unroll
-        for (int q = 0; q < N; q++) base[q] = tot[q] ? atomicAdd(counter[q], tot[q]) : 0u;
-#pragma unroll
-        for (int q = 0; q < N; q++) L[APP_W * N + q] = base[q];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < N; q++)
-        slot[q] = L[APP_W * N + q] + L[APP_W * q + wave] +
-                  __builtin_amdgcn_mbcnt_hi((uint32_t)(m[q] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m[q], 0u));
-}
-
+// (block_append_n, the block-aggregated append of one iteration: append.hpp)
 // block_append_n with the slots reserved app_chunk at a time (WfArgs::app_chunk): thread 0 keeps each
 // queue's current chunk (cb: its first slot, cu: slots used; cu = C and cb anything before the first) in its
 // registers and reserves a new chunk only when an iteration's appends do not fit the current one; the
@@ -1541,6 +1497,7 @@ static bool camera_fuses(const WfVariant &v, const RenderArgs &A, const WfArgs &
     return W.cam_fused && v.packet && !A.eye_on_split && camera_state_lean(W);
 }
 bool wf_variant_culls(int variant) { return wf_build(variant) && wf_build(variant)->cull; }
+bool wf_variant_leaf_cull(int variant) { return wf_build(variant) && wf_build(variant)->lc != 0; }
 bool wf_variant_available(int variant) { return wf_build(variant) != nullptr; }
 
 // One thread per leaf reference: its cull box for this render's camera (camcull.hpp),
@@ -1609,6 +1566,23 @@ void wf_trace_geometry(int variant, int num_cus, uint32_t &block, uint32_t &bloc
     const WfVariant &v = wf_build_or_ref(variant);
     block = 256;
     blocks = (uint32_t)(num_cus > 0 ? num_cus : 256) * (uint32_t)v.waves_per_simd; // 4 SIMDs, 4 waves/block
+}
+
+// One trace launch over a ray-query queue (queries.hip / cabi.cpp cr_intersect_device): the generic closest
+// or shadow wf_trace of the scene's default build `variant` (cull: QR_DEFAULT queries) or of build 44's
+// fat kernels without a leaf cull (QR_FAT queries).  Never a tc::Fixed instantiation (they assume resolve
+// marks: the queries' W has vis_mark 0 and vis_dw 0, so shadow answers land in occ[slot]), never a
+// shadow_dead one (a query queue has no dead entries) and never generation 1 (the camera refill).
+int launch_query_trace(const RenderArgs &A, const WfArgs &W, uint32_t g, bool shadow, bool cull, int variant,
+                       int num_cus, hipStream_t st) {
+    const WfVariant *v = wf_build(cull ? variant : 44);
+    if (!v || g < 2 || g >= WF_G || W.vis_mark || W.vis_dw || W.xcd) return (int)hipErrorInvalidValue;
+    uint32_t blk, blocks;
+    wf_trace_geometry(cull ? variant : 44, num_cus, blk, blocks);
+    if (blk != 256 || W.gstride < blk * blocks) return (int)hipErrorInvalidConfiguration;
+    const size_t lds = (size_t)v->ring * blk * sizeof(uint2);
+    hipLaunchKernelGGL(shadow ? v->shadow : v->closest, dim3(blocks), dim3(blk), lds, st, A, W, g);
+    return (int)hipGetLastError();
 }
 
 // Sorts the queue of n rays whose keys wf_shade wrote into key / perm set `set`

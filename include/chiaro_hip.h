@@ -36,6 +36,9 @@
  *                        communicator from a unique id the caller distributes).
  *   cr_intersect         KDTree::intersectRay       (src/kdtree.cpp:210-216)
  *   cr_intersect_shadow  KDTree::intersectShadowRay (src/kdtree.cpp:283-290)
+ *   cr_intersect_device / cr_intersect_shadow_device
+ *                        the same two queries on device arrays, on a caller-supplied HIP
+ *                        stream, through the render's trace kernels.
  *
  * Threading: one cr_ctx per GPU, not thread-safe; calls on one ctx are serialised.
  */
@@ -262,6 +265,29 @@ int cr_intersect(cr_ctx *ctx, uint32_t n, const float *orig, const float *dir, u
                  float *bary, float *dist);
 int cr_intersect_shadow(cr_ctx *ctx, uint32_t n, const float *orig, const float *dir, const float *dist,
                         const uint32_t *light_tri, uint32_t *occluded);
+/* The same queries on device arrays, stream-ordered on the caller's HIP stream `stream` (0: the null stream):
+ * the calls enqueue their work and return without synchronising the host, and the results arrive in input
+ * order.  Layouts and meaning are cr_intersect's / cr_intersect_shadow's: [n][3] origins and directions
+ * (directions need not be normalised, distances are in units of the direction), hit / occluded [n] as 0 / 1;
+ * d_tri [n], d_bary [n][2] and d_dist [n] may be null and are left untouched where the query misses.
+ * Outputs must not alias inputs.  Any n up to 2^32 - 2; batches longer than one chunk (option "query_chunk")
+ * run as several chunks on the stream.  n == 0: CR_OK, nothing launched; a null required pointer:
+ * CR_E_INVALID; no scene: CR_E_NOSCENE; no device: CR_E_HIP.
+ * Batches of at least "query_trace_min" queries run through the render's trace kernels: every query is routed
+ * by what the kernels' exactness rests on (csrc/queryroute.hpp) -- the scene's default trace
+ * build for finite rays whose origin lies inside the scene's padded box widened by 1 per side (and within
+ * the coordinate bound the leaf cull records were padded for), trace build 44's closest / shadow kernels,
+ * which have no leaf cull, for other finite rays (a sensor outside the scene), and cr_intersect's per-thread
+ * kernel for anything else (any NaN or infinity; a light id with bit 31 set) -- so every query answers bit
+ * for bit as cr_intersect / cr_intersect_shadow do.  The ctx keeps query buffers of its own (nothing is
+ * shared with a render in flight on another stream) and an event recorded after each call: a call that has to
+ * regrow the buffers, or that runs on another stream than the last one, waits for it first.  The buffers
+ * the caller passes must stay valid until the work has run.  cr_get_counters is not touched. */
+int cr_intersect_device(cr_ctx *ctx, uint32_t n, const float *d_orig, const float *d_dir, uint32_t *d_hit,
+                        uint32_t *d_tri, float *d_bary, float *d_dist, void *stream);
+int cr_intersect_shadow_device(cr_ctx *ctx, uint32_t n, const float *d_orig, const float *d_dir,
+                               const float *d_dist, const uint32_t *d_light_tri, uint32_t *d_occluded,
+                               void *stream);
 
 int cr_get_counters(cr_ctx *ctx, cr_counters *out);
 /* Device time (ms) of the last render kernel, HIP events on its own stream. */
@@ -284,12 +310,28 @@ typedef struct cr_trace_stats {
     uint64_t chunked_shades;
 } cr_trace_stats;
 int cr_get_trace_stats(cr_ctx *ctx, cr_trace_stats *out);
-/* Kernel variant / tuning knobs: "kernel" (0 = persistent wave-regeneration,
- * 1 = one-thread-per-pixel), "variant" (persistent-kernel build, 0 = default),
- * "refill" (1..64: idle lanes of a wave that trigger a path-state step in the
- * dynamic-fetch variants), "counters" (1 = also count inner/leaf/tritest and
- * the wave_* diagnostics; 0 = only the per-query tallies, for timed launches),
- * "block", "waves_per_cu".  Returns CR_OK or CR_E_INVALID.
+/* Options; CR_OK, or CR_E_INVALID for an unknown key or a value out of range.  The defaults are the measured
+ * ones; results are bit-identical under every value unless marked "measurement only".
+ *   render kernel   "kernel" (2: the wavefront path tracer, the only one), "variant" (trace build, -1: by scene
+ *                   size, see cr_trace_build_available), "counters" (1: the counting build, every cr_counters
+ *                   field; 0: the lean timed build), "perf_counters", "diag_kinds", "lc_debug" and
+ *                   "wf_measure_skip" (measurement only), "lc_min", "desc_quorum", "refill", "refill_shadow",
+ *                   "refill_camera" (1..64 idle lanes of a wave that trigger a refill; 0: default)
+ *   wavefront       "wf_paths", "wf_lanes", "wf_tail_min", "wf_tail_overlap", "wf_tail_waves", "wf_cam_lean",
+ *                   "wf_cam_fuse", "wf_ctl_ray", "wf_vis_dw", "wf_vis_mark", "wf_nee_skip", "wf_shade_waves",
+ *                   "wf_shade_block", "wf_app_chunk", "wf_resolve_paths", "wf_xcd", "wf_side_priority"
+ *   queue order     "wf_sort" (-1: by scene size), "wf_sort_min", "wf_sort_g1", "wf_sort_tile", "wf_dir_res",
+ *                   "wf_dir_res_shadow", "wf_world_keys", "wf_world_bits", "wf_leaf_keys", "wf_leaf_shift"
+ *   buffers, scene  "sample_buf_bytes", "sum_lds", "sum_staged", "node_bfs" (applies at the next upload),
+ *                   "comm_timeout_ms"
+ *   device queries  (cr_intersect_device / cr_intersect_shadow_device)
+ *                   "query_route": 0 automatic per-query routing, 1 every query through cr_intersect's
+ *                   per-thread kernel, 2 the kernels without the leaf cull for every query that qualifies for
+ *                   a trace kernel; "query_sort": -1 automatic (scenes of at least 1024 triangles, chunks of
+ *                   at least 2^22 queries), 0 queues traced in append order, 1 sorted by origin and
+ *                   direction; "query_chunk": queries per chunk (256 .. 2^24, the default);
+ *                   "query_trace_min": batches shorter than this go to the per-thread kernel whole
+ *                   (default 65536, the measured crossover).
  * The default trace builds (59 / 44) run closest and shadow trace kernels with "wf_vis_mark" 1, no
  * overlapped tail ("wf_tail_overlap" 0) and "lc_debug" 0 fixed at compile time; a non-default value of
  * one of these selects the build's generic trace kernels for the launches it applies to (the same build
@@ -300,8 +342,9 @@ int cr_set_option(cr_ctx *ctx, const char *key, int64_t value);
  * shapes (what staging a wave's leaves in LDS would load) and a per-lane census of
  * repeated any-segment triangle misses.  Up to n of the DIAG_* values (csrc/kernels.hpp). */
 int cr_get_diag(cr_ctx *ctx, uint64_t *out, int n);
-/* Performed work of the last render with option "perf_counters" 1 (trace builds 18 / 26 / 40 / 42 /
- * 43 / 44 -- the defaults are 43 and 44 -- instantiated with counters; measurement only): per trace kind k (0 camera, 1 closest, 2 shadow,
+/* Performed work of the last render with option "perf_counters" 1 (trace builds 18 / 26 / 40 / 42 / 43 / 44 /
+ * 49 / 53 / 54 / 59 -- the defaults are 59 and 44 -- have instances with these counters, 59 counting through
+ * 54's; measurement only): per trace kind k (0 camera, 1 closest, 2 shadow,
  * 3 tail) the PERF_N = 12 values out[12k + i] -- queries, inner-node steps, leaves reached, leaf
  * cull records evaluated, triangle tests executed (all per ray), bytes of vector-memory loads and
  * stores (per lane), bytes of scalar-memory loads (per wave), wave iterations, and the shape of
@@ -309,11 +352,12 @@ int cr_get_diag(cr_ctx *ctx, uint64_t *out, int n);
  * csrc/kernels.hpp).  Where the counting build ("counters" 1) counts the reference algorithm's
  * work, these count what the culling kernels actually do.  Up to n values. */
 int cr_get_perf(cr_ctx *ctx, uint64_t *out, int n);
-/* 1 when wavefront trace build `build` (option "variant" with "kernel" 2) is compiled in:
- * the default compile holds 0, 15, 18 and 26 (the default); `make ALL_VARIANTS=1` every
- * measured build.  A render with a missing build returns CR_E_INVALID. */
+/* 1 when wavefront trace build `build` (option "variant") is compiled in: 0 (the plain reference build), 15,
+ * 18, 26, 40, 42, 43, 44 (the default below 65536 triangles), 49, 53, 54 and 59 (the default from 65536
+ * triangles on); the other measured builds are gone (DESIGN.md keeps their numbers).  A render with a
+ * missing build returns CR_E_INVALID. */
 int cr_trace_build_available(int build);
-/* The wavefront trace build the last render on ctx ran (its "variant": the scene-size default 43 / 44
+/* The wavefront trace build the last render on ctx ran (its "variant": the scene-size default 59 / 44
  * unless set), -1 when it was the counting build ("counters" 1), -2 when it was not a wavefront render
  * (or none has run).  Lets a caller name the kernels a result came from (bench.py, smoke()). */
 int cr_last_trace_build(cr_ctx *ctx);
