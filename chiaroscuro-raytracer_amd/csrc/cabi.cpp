@@ -5,6 +5,7 @@
 // per-launch HIP events.  No C++ exception or hipError_t crosses the ABI.
 #include "ctx.hpp"
 #include "leafcull.hpp"
+#include "wfplan.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -76,11 +77,7 @@ int grow(cr_ctx *c, void **buf, size_t &cap, size_t need) {
 
 // scenes with fewer triangles default to trace build 18 instead of 26 (fill_args)
 const uint32_t LEAF_CULL_MIN_TRIS = 65536;
-// scenes with fewer triangles trace their queues in append order (wf_sort -1, the default): on a
-// handful of triangles the whole scene stays in cache whatever the order, and the sort plus the
-// trace's reads through the permutation cost more than coherence gains (round 4, cornell_box 1024^2 x
-// 500 spp, two interleaved rounds: sorted 9050 / 8894, unsorted 11140 / 11130 Mray/s)
-const uint32_t SORT_MIN_TRIS = 1024;
+using cr::SORT_MIN_TRIS; // (wfplan.hpp: scenes below it trace their queues in append order)
 
 // The scene's default trace build: 59 from LEAF_CULL_MIN_TRIS triangles on, else 44 (the history: fill_args).
 int default_trace_build(const cr_ctx *c) { return c->n_tris >= LEAF_CULL_MIN_TRIS ? 59 : 44; }
@@ -177,23 +174,22 @@ void fill_args(cr_ctx *c, cr::RenderArgs &A, const cr_camera *cam, const cr_rend
         if (std::binary_search(c->splits[a].begin(), c->splits[a].end(), cam->eye[a])) A.eye_on_split = 1;
 }
 
-// path slots one wavefront chunk may hold: ~45% of the HBM that was free (plus the chunk buffers then
-// held) when the ctx first asked after its scene upload.  Kept until the next upload: the plan of a pass group (cr_layers_per_group,
-// cr_layers_per_pass) must not change as this ctx's own buffers grow, or ranks that asked at different
-// moments would plan different groups and their per-layer gathers would not pair up
-// wf_shade may append in chunks (WfArgs::app_chunk: the queues traced in append order, or a forced chunk):
-// only then do the queue arrays carry spare slots -- a sorted scene's path cap, and with it the pieces of a
-// pass group, stays what it was
-bool wf_chunked(const cr_ctx *c) {
-    return c->wf_app_chunk || c->wf_sort == 0 || (c->wf_sort < 0 && c->n_tris < SORT_MIN_TRIS);
-}
+// The path cap of this ctx (wfplan.hpp wf_path_cap_of): the HBM budget is queried once, at the first plan after
+// a scene upload, and kept
 uint64_t wf_path_cap(cr_ctx *c, int k) {
     if (!c->wf_mem_budget) {
         size_t freeb = 0, totalb = 0;
         if (hipMemGetInfo(&freeb, &totalb) != hipSuccess) return ~0ull;
         c->wf_mem_budget = freeb + c->wf_bytes + c->wf2_bytes;
     }
-    return (uint64_t)(c->wf_mem_budget * 0.45) / cr::wf_bytes_per_path(k, wf_chunked(c));
+    return cr::wf_path_cap_of(c->wf_mem_budget, k, cr::wf_chunked(*c, c->n_tris));
+}
+
+// the host's copy of the device counters as cr_counters
+cr_counters counters_of(const unsigned long long *h) {
+    return cr_counters{h[0], h[1],  h[2],  h[3],  h[4],  h[5],  h[6],  h[7], h[8],
+                       h[9], h[10], h[11], h[12], h[13], h[14], h[15], h[16],
+                       h[17], h[18], h[19], h[20], h[21], h[cr::CTR_NEE]};
 }
 
 int run_render(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, float *out, int mode, hipStream_t st,
@@ -206,9 +202,6 @@ int run_render(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, float
     HIPCHK(hipSetDevice(c->device));
     cr::RenderArgs A{};
     fill_args(c, A, cam, p, out, mode);
-    // nl layers in one pass: every item holds nl * spp samples (layer p->layer + s / spp)
-    const uint64_t spp_pass = (uint64_t)p->spp * nl;
-    if (spp_pass >= (1ull << 31)) return fail(c, CR_E_INVALID, "layers x spp too large");
     A.nl = nl;
     A.layer_stride = (uint64_t)cr_tiles_for_rank(p, 0) * A.tile * A.tile * 3;
     if (piece_m > 1) {
@@ -225,230 +218,77 @@ int run_render(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, float
                                      "49, 53, 54 and 59 only, without the counting build");
     c->last_build = c->kernel == 2 ? (c->full_counters ? -1 : A.variant) : -2;
     HIPCHK(hipMemsetAsync(c->d_counters, 0, cr::CTR_SLOTS * sizeof(unsigned long long), st));
-    {
-        const bool wf = true; // (the wavefront path tracer is the render kernel)
-        uint32_t blk, blocks;
-        cr::wf_trace_geometry(c->full_counters ? -1 : A.variant, c->num_cus, blk, blocks);
-        A.gstride = blk * blocks;
-        // samples per chunk: the per-sample buffer stays within SAMPLE_BUF_BYTES
-        // and the work index within 31 bits
-        const uint64_t per_sample = (uint64_t)A.n_items * 12u;
-        uint64_t chunk = std::max<uint64_t>(1, c->sample_buf / std::max<uint64_t>(per_sample, 1));
-        chunk = std::min<uint64_t>(chunk, std::max<uint64_t>(1, (1ull << 31) / std::max<uint32_t>(A.n_items, 1)));
-        chunk = std::min<uint64_t>(chunk, spp_pass);
-        // a chunk of a multiple of 16 samples (sum_samples_lds stages 16 at a time and needs runs of a
-        // multiple of 4; the last chunk then has spp mod 4 == its own mod 4)
-        if (chunk < spp_pass && chunk >= 16) chunk &= ~(uint64_t)15;
-        const bool chunked = chunk < spp_pass;
-        if (nl > 1 && chunked) return fail(c, CR_E_INVALID, "layers per pass: the samples do not fit one buffer");
-        // wavefront: a second stack-overflow area for the closest trace that runs beside a
-        // shadow trace, per lane
-        if (cr::gstack_bytes(c->stack_depth, A.gstride) >= (1ull << 32)) // (gstack_at's 32-bit offsets)
-            return fail(c, CR_E_INVALID, "stack-overflow area above 4 GiB");
-        if (int r = grow(c, &c->d_gstack, c->gstack_bytes, 2 * c->wf_lanes * cr::gstack_bytes(c->stack_depth, A.gstride)))
-            return r;
-        // large renders reserve the whole sample budget at once: a later pass of another shape (a pass
-        // group's frame piece, cr_render_layers) then reuses the buffer instead of regrowing it
-        {
-            const uint64_t need = per_sample * chunk;
-            if (int r = grow(c, &c->d_samples, c->samples_bytes, need * 4 > c->sample_buf ? std::max<uint64_t>(need, c->sample_buf) : need))
-                return r;
-        }
-        if (chunked)
-            if (int r = grow(c, &c->d_run, c->run_bytes, per_sample)) return r;
-        A.gstack = (uint2 *)c->d_gstack;
-        A.samples = (float *)c->d_samples;
-        A.run = (float *)c->d_run;
-        cr::WfArgs W{};
-        cr::WfArgs W2{};
-        const int lanes = c->wf_lanes;
-        {
-            // path slots per wavefront chunk, and the queues / state carved from one buffer
-            // per lane ... at most ~45% of the currently free HBM in all (the buffers are
-            // reused, so only a growth needs the headroom).  Two lanes: two chunks in flight,
-            // the second starting once the first is past its camera-ray trace.
-            uint64_t P = (uint64_t)A.n_items * chunk;
-            if (lanes == 2) P = (P + 1) / 2;
-            P = std::min<uint64_t>(P, c->wf_paths);
-            {
-                const uint64_t cap = wf_path_cap(c, p->k) / (uint64_t)lanes;
-                P = std::max<uint64_t>(std::min<uint64_t>(P, cap), std::min<uint64_t>(P, 1u << 20));
-            }
-            const size_t f4 = 16 * (size_t)P;
-            // queue-indexed arrays hold qspare more slots: the dead entries of wf_shade's chunked appends
-            // (WfArgs::app_chunk; at most one partial chunk per block and queue)
-            // (option "wf_app_chunk" forces a chunk size: room for it on every block)
-            const uint64_t forced = c->wf_app_chunk ? (uint64_t)cr::wf_shade_blocks(c->num_cus, c->wf_shade_waves) * c->wf_app_chunk : 0;
-            const bool chunked = wf_chunked(c);
-            auto spare_for = [&](uint64_t Pn) {
-                return chunked ? std::max<uint64_t>(std::min<uint64_t>(Pn / 8, 8u << 20), forced) : (uint64_t)0;
-            };
-            const uint64_t Q = P + spare_for(P);
-            const size_t fq = 16 * (size_t)Q;
-            // queue sorting: by default for scenes of at least SORT_MIN_TRIS triangles only (wf_sort -1)
-            const int sort = c->wf_sort >= 0 ? c->wf_sort : (c->n_tris >= SORT_MIN_TRIS ? 1 : 0);
-            // queue-sort keys: (pixel sub-tile, octahedral direction bin)
-            const uint32_t T = A.tile, sub = (T + (1u << c->wf_sort_tile) - 1) >> c->wf_sort_tile;
-            const uint64_t nkeys = (uint64_t)(A.n_items / (T * T)) * sub * sub * c->wf_dir_res * c->wf_dir_res;
-            int key_bits = 1;
-            while (key_bits < 32 && (1ull << key_bits) < nkeys) key_bits++;
-            const int key_bits_pixel = key_bits;
-            const uint64_t nworld = (1ull << (3 * c->wf_world_bits)) * c->wf_dir_res * c->wf_dir_res;
-            while (c->wf_world_keys && key_bits < 32 && (1ull << key_bits) < nworld) key_bits++;
-            // leaf keys: (leaf node >> wf_leaf_shift, direction bin); the direction grid is halved
-            // until the key fits 32 bits (the sponza stand-in keeps 128 x 128 bins at shift 1)
-            auto leaf_width = [&](uint64_t dres) {
-                int b = 1;
-                while (b < 40 && (1ull << b) < (((uint64_t)A.S.n_nodes >> c->wf_leaf_shift) + 1) * dres * dres) b++;
-                return b;
-            };
-            uint32_t dres_l = c->wf_dir_res;
-            while (dres_l > 8 && leaf_width(dres_l) > 32) dres_l >>= 1;
-            const int leaf_bits = leaf_width(dres_l);
-            const bool leaf_keys = c->wf_leaf_keys && leaf_bits <= 32;
-            // the shadow queues' leaf keys may use another direction grid (option "wf_dir_res_shadow")
-            uint32_t dres_s = c->wf_dir_res_shadow ? c->wf_dir_res_shadow : dres_l;
-            while (dres_s > 1 && leaf_width(dres_s) > 32) dres_s >>= 1;
-            const int leaf_bits_s = leaf_width(dres_s);
-            // (leaf keys replace the pixel and world keys in every queue: their width alone sets the
-            // digit passes)
-            if (leaf_keys) key_bits = leaf_bits;
-            // bytes of the buffers of a chunk of Pn paths with kb-bit sort keys
-            auto need_for = [&](uint64_t Pn, int kb) -> size_t {
-                const uint64_t Qn = Pn + spare_for(Pn);
-                const size_t st = sort ? cr::wf_sort_tmp_bytes((uint32_t)Qn, kb) : 0;
-                return (4 + 2 + 2) * 16 * (size_t)Qn + 8 * (size_t)Qn +
-                       (cr::WF_STATE + 2 * (size_t)p->k) * 16 * (size_t)Pn + 9 * (size_t)Pn +
-                       (sort ? 32 * (size_t)Qn + st : 0) + cr::WF_CNT * sizeof(uint32_t) + 8192;
-            };
-            const size_t sort_tmp = sort ? cr::wf_sort_tmp_bytes((uint32_t)Q, key_bits) : 0;
-            const size_t need = need_for(P, key_bits);
-            // a chunk of more than a quarter of the path cap reserves the buffers of a whole-cap chunk
-            // with the widest keys, so passes of other sizes (a pass group's frame pieces, the next
-            // layer) reuse them instead of regrowing ~100 GB inside a timed render
-            size_t need_alloc = need;
-            {
-                const uint64_t pcap = std::min<uint64_t>(c->wf_paths, wf_path_cap(c, p->k) / (uint64_t)lanes);
-                if (P * 4 > pcap) need_alloc = std::max(need, need_for(std::max<uint64_t>(P, pcap), 32));
-            }
-            if (int r = grow(c, &c->d_wf, c->wf_bytes, need_alloc)) return r;
-            if (lanes == 2)
-                if (int r = grow(c, &c->d_wf2, c->wf2_bytes, need_alloc)) return r;
-            auto carve = [&](void *base, cr::WfArgs &W, int lane) {
-                char *b = (char *)base;
-                auto take = [&](size_t bytes) {
-                    char *r = b;
-                    b += (bytes + 255) & ~(size_t)255;
-                    return r;
-                };
-                W.ray[0] = (float4 *)take(2 * fq);
-                W.ray[1] = (float4 *)take(2 * fq);
-                W.hit[0] = (uint4 *)take(fq);
-                W.hit[1] = (uint4 *)take(fq);
-                W.sray = (float4 *)take(2 * fq);
-                W.ps = (float4 *)take(cr::WF_STATE * f4);
-                W.dw = (float4 *)take(2 * (size_t)p->k * f4);
-                W.sexcl = (uint32_t *)take(4 * (size_t)Q);
-                W.occ = (uint32_t *)take(4 * (size_t)Q);
-                W.qspare = (uint32_t)(Q - P);
-                W.app_force = (uint32_t)c->wf_app_chunk;
-                W.shade_block = (uint32_t)c->wf_shade_block;
-                W.cnt = (uint32_t *)take(cr::WF_CNT * sizeof(uint32_t));
-                W.cxy = (float2 *)take(8 * (size_t)P);
-                W.mark = (uint8_t *)take((size_t)P);
-                W.shade_waves = c->wf_shade_waves;
-                W.sort = sort && nkeys <= (1ull << 32);
-                W.key_bits = key_bits;
-                W.key_bits_pixel = key_bits_pixel;
-                W.sort_min = c->wf_sort_min;
-                W.sort_tile = c->wf_sort_tile;
-                W.dir_res = leaf_keys ? dres_l : c->wf_dir_res;
-                W.dir_res_s = leaf_keys ? dres_s : c->wf_dir_res;
-                W.key_bits_s = leaf_keys ? leaf_bits_s : key_bits;
-                W.world_keys = nworld <= (1ull << 32) ? c->wf_world_keys : 0;
-                W.world_bits = c->wf_world_bits;
-                W.tail_min = c->wf_tail_min;
-                W.xcd = c->wf_xcd;
-                W.leaf_keys = leaf_keys ? 1 : 0;
-                W.leaf_shift = c->wf_leaf_shift;
-                W.resolve_paths = c->wf_resolve_paths;
-                W.measure_skip = c->wf_measure_skip;
-                W.tail_overlap = c->wf_tail_overlap;
-                W.sort_g1 = c->wf_sort_g1;
-                W.cam_lean = c->wf_cam_lean;
-                W.cam_fused = c->wf_cam_fuse;
-                W.ctl_ray = c->wf_ctl_ray;
-                W.vis_dw = c->wf_vis_dw;
-                W.vis_mark = c->wf_vis_mark && !c->wf_tail_overlap && p->k <= 63 ? 1 : 0;
-                W.nee_skip = c->wf_nee_skip;
-                W.tail_waves = c->wf_tail_waves;
-                if (sort) {
-                    for (int q = 0; q < 2; q++)
-                        for (int i = 0; i < 2; i++) {
-                            W.key[q][i] = (uint32_t *)take(4 * (size_t)Q);
-                            W.perm[q][i] = (uint32_t *)take(4 * (size_t)Q);
-                        }
-                    W.sort_tmp = take(sort_tmp);
-                    W.sort_tmp_bytes = sort_tmp;
-                }
-                const size_t area = (size_t)c->stack_depth * A.gstride;
-                W.gstack = A.gstack + 2 * (size_t)lane * area;
-                W.gstack2 = W.gstack + area;
-                W.gstride = A.gstride;
-                W.P = (uint32_t)P;
-            };
-            carve(c->d_wf, W, 0);
-            if (lanes == 2) carve(c->d_wf2, W2, 1);
-        }
-        // screen-space cull boxes of this camera for the camera-ray trace (camcull.hpp),
-        // computed inside the timed region of every render
-        // (built for triangle-less scenes too: the culling kernels read them unconditionally, and
-        // with n_refs + 4 empty boxes every sample is outside)
-        const bool cull = wf && !c->full_counters && cr::wf_variant_culls(A.variant);
-        if (cull) {
-            if (int r = grow(c, &c->d_cull, c->cull_bytes, 16 * ((size_t)c->n_refs + 4))) return r;
-            if (int r = grow(c, &c->d_cull_node, c->cull_node_bytes, 16 * (size_t)c->S.n_nodes)) return r;
-        }
-        A.cull = cull ? (const float4 *)c->d_cull : nullptr;
-        A.cull_node = cull ? (const float4 *)c->d_cull_node : nullptr;
-        c->tev.n = 0;
-        c->tev.chunked = 0;
-        HIPCHK(hipEventRecord(c->ev0, st));
-        if (cull)
-            if (int e = cr::launch_cam_cull(A, c->n_refs, (float4 *)c->d_cull, (float4 *)c->d_cull_node, c->d_levels,
-                                            (const uint32_t(*)[2])c->levels.data(), (int)c->levels.size(), st))
-                return hip_fail(c, (hipError_t)e, "cull-box kernel launch");
-        for (uint32_t s0 = 0; s0 < spp_pass; s0 += (uint32_t)chunk) {
-            A.s0 = s0;
-            A.s_count = (uint32_t)std::min<uint64_t>(chunk, spp_pass - s0);
-            A.n_work = A.n_items * A.s_count;
-            int e = 0;
-            if (lanes == 2) {
-                cr::WfLane L[2] = {{W, st, c->wfs.side, c->wfs.fork, c->wfs.join, c->lane_ev[0], c->hcnt},
-                                   {W2, c->stream2, c->side2, c->fork2, c->join2, c->lane_ev[1], c->hcnt + 2}};
-                e = cr::run_wavefront_lanes(A, L, 2, c->num_cus, st, &c->tev);
-            } else {
-                const uint32_t P = W.P;
-                for (uint32_t w0 = 0; w0 < A.n_work && !e; w0 += P) {
-                    W.w0 = w0;
-                    W.P = std::min(P, A.n_work - w0);
-                    HIPCHK(hipMemsetAsync(W.cnt, 0, cr::WF_CNT * sizeof(uint32_t), st));
-                    e = cr::launch_wavefront_chunk(A, W, c->num_cus, st, c->wfs, &c->tev);
-                }
-                W.P = P;
-            }
-            if (!e) e = cr::launch_sum_samples(A, s0 == 0, s0 + A.s_count == spp_pass, st, c->sum_lds, c->sum_staged != 0);
-            if (e) return hip_fail(c, (hipError_t)e, "render kernel launch");
-        }
-        HIPCHK(hipEventRecord(c->ev1, st));
+    uint32_t blk, blocks;
+    cr::wf_trace_geometry(c->full_counters ? -1 : A.variant, c->num_cus, blk, blocks);
+    A.gstride = blk * blocks;
+    // the plan of the pass (wfplan.hpp): sample chunks, path chunks, key widths, buffer sizes
+    // (the spare slots of a forced append chunk alone depend on wf_shade's grid: an occupancy query)
+    const uint32_t shade_blocks = c->wf_app_chunk ? cr::wf_shade_blocks(c->num_cus, c->wf_shade_waves) : 0u;
+    const cr::WfPlanIn in{*c, A.n_items, p->spp, nl, p->k, A.tile, c->n_tris, A.S.n_nodes, c->stack_depth, A.gstride,
+                          shade_blocks, wf_path_cap(c, p->k)};
+    const cr::WfPlan pl = cr::wf_plan(in);
+    if (pl.code) return fail(c, pl.code, pl.msg);
+    const int lanes = c->wf_lanes;
+    if (int r = grow(c, &c->d_gstack, c->gstack_bytes, pl.gstack_bytes)) return r;
+    if (int r = grow(c, &c->d_samples, c->samples_bytes, pl.samples_bytes)) return r;
+    if (pl.chunked)
+        if (int r = grow(c, &c->d_run, c->run_bytes, pl.run_bytes)) return r;
+    if (int r = grow(c, &c->d_wf, c->wf_bytes, pl.need_alloc)) return r;
+    if (lanes == 2)
+        if (int r = grow(c, &c->d_wf2, c->wf2_bytes, pl.need_alloc)) return r;
+    A.gstack = (uint2 *)c->d_gstack;
+    A.samples = (float *)c->d_samples;
+    A.run = (float *)c->d_run;
+    cr::WfArgs W{};
+    cr::WfArgs W2{};
+    cr::wf_bind(in, pl, c->d_wf, A.gstack, 0, W);
+    if (lanes == 2) cr::wf_bind(in, pl, c->d_wf2, A.gstack, 1, W2);
+    // screen-space cull boxes of this camera for the camera-ray trace (camcull.hpp),
+    // computed inside the timed region of every render
+    // (built for triangle-less scenes too: the culling kernels read them unconditionally, and
+    // with n_refs + 4 empty boxes every sample is outside)
+    const bool cull = !c->full_counters && cr::wf_variant_culls(A.variant);
+    if (cull) {
+        if (int r = grow(c, &c->d_cull, c->cull_bytes, 16 * ((size_t)c->n_refs + 4))) return r;
+        if (int r = grow(c, &c->d_cull_node, c->cull_node_bytes, 16 * (size_t)c->S.n_nodes)) return r;
     }
+    A.cull = cull ? (const float4 *)c->d_cull : nullptr;
+    A.cull_node = cull ? (const float4 *)c->d_cull_node : nullptr;
+    c->tev.n = 0;
+    c->tev.chunked = 0;
+    HIPCHK(hipEventRecord(c->ev0, st));
+    if (cull)
+        if (int e = cr::launch_cam_cull(A, c->n_refs, (float4 *)c->d_cull, (float4 *)c->d_cull_node, c->d_levels,
+                                        (const uint32_t(*)[2])c->levels.data(), (int)c->levels.size(), st))
+            return hip_fail(c, (hipError_t)e, "cull-box kernel launch");
+    for (uint32_t s0 = 0; s0 < pl.spp_pass; s0 += (uint32_t)pl.chunk) {
+        A.s0 = s0;
+        A.s_count = (uint32_t)std::min<uint64_t>(pl.chunk, pl.spp_pass - s0);
+        A.n_work = A.n_items * A.s_count;
+        int e = 0;
+        if (lanes == 2) {
+            cr::WfLane L[2] = {{W, st, c->wfs.side, c->wfs.fork, c->wfs.join, c->lane_ev[0], c->hcnt},
+                               {W2, c->stream2, c->side2, c->fork2, c->join2, c->lane_ev[1], c->hcnt + 2}};
+            e = cr::run_wavefront_lanes(A, L, 2, c->num_cus, st, &c->tev);
+        } else {
+            const uint32_t P = W.P;
+            for (uint32_t w0 = 0; w0 < A.n_work && !e; w0 += P) {
+                W.w0 = w0;
+                W.P = std::min(P, A.n_work - w0);
+                HIPCHK(hipMemsetAsync(W.cnt, 0, cr::WF_CNT * sizeof(uint32_t), st));
+                e = cr::launch_wavefront_chunk(A, W, c->num_cus, st, c->wfs, &c->tev);
+            }
+            W.P = P;
+        }
+        if (!e) e = cr::launch_sum_samples(A, s0 == 0, s0 + A.s_count == pl.spp_pass, st, c->sum_lds, c->sum_staged != 0);
+        if (e) return hip_fail(c, (hipError_t)e, "render kernel launch");
+    }
+    HIPCHK(hipEventRecord(c->ev1, st));
     unsigned long long h[cr::CTR_SLOTS];
     HIPCHK(hipMemcpyAsync(h, c->d_counters, sizeof(h), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1));
-    c->last = cr_counters{h[0], h[1],  h[2],  h[3],  h[4],  h[5],  h[6],  h[7], h[8],
-                          h[9], h[10], h[11], h[12], h[13], h[14], h[15], h[16],
-                          h[17], h[18], h[19], h[20], h[21], h[cr::CTR_NEE]};
+    c->last = counters_of(h);
     for (int i = 0; i < cr::DIAG_N; i++) c->last_diag[i] = h[cr::CTR_DIAG + i];
     for (int i = 0; i < cr::TK_N * cr::PERF_N; i++) c->last_perf[i] = h[cr::CTR_PERF + i];
     c->last_trace = cr_trace_stats{};
@@ -827,6 +667,19 @@ uint32_t cr_tiles_for_rank(const cr_render_params *p, uint32_t rank) {
     return nt > rank ? (nt - rank + p->nranks - 1) / p->nranks : 0;
 }
 
+// The progressive accumulator at `elems` floats: reallocated when a frame of another size arrives (zero: a
+// render starts a new accumulation; cr_set_accumulator overwrites it anyway)
+static int size_accumulator(cr_ctx *c, size_t elems, bool zero) {
+    if (elems == c->accum_elems) return CR_OK;
+    if (c->d_accum) hipFree(c->d_accum);
+    c->d_accum = nullptr;
+    c->accum_elems = 0;
+    if (hipMalloc(&c->d_accum, elems * sizeof(float)) != hipSuccess) return fail(c, CR_E_OOM, "accumulator");
+    c->accum_elems = elems;
+    if (zero) HIPCHK(hipMemset(c->d_accum, 0, elems * sizeof(float)));
+    return CR_OK;
+}
+
 int cr_render(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, float *accum_rgb_out) {
     if (!c) return CR_E_INVALID;
     if (c->device < 0) return fail(c, CR_E_HIP, c->err.empty() ? "no device" : c->err);
@@ -837,14 +690,7 @@ int cr_render(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, float 
     if (rc) return rc;
     HIPCHK(hipSetDevice(c->device));
     const size_t elems = (size_t)q.xres * q.yres * 3;
-    if (elems != c->accum_elems) {
-        if (c->d_accum) hipFree(c->d_accum);
-        c->d_accum = nullptr;
-        c->accum_elems = 0;
-        if (hipMalloc(&c->d_accum, elems * sizeof(float)) != hipSuccess) return fail(c, CR_E_OOM, "accumulator");
-        c->accum_elems = elems;
-        HIPCHK(hipMemset(c->d_accum, 0, elems * sizeof(float)));
-    }
+    if (int r = size_accumulator(c, elems, true)) return r;
     rc = run_render(c, cam, &q, c->d_accum, cr::MODE_BLEND, c->stream);
     if (rc) return rc;
     HIPCHK(hipMemcpy(accum_rgb_out, c->d_accum, elems * sizeof(float), hipMemcpyDeviceToHost));
@@ -901,14 +747,7 @@ int cr_render_layers(cr_ctx *c, const cr_camera *cam, const cr_render_params *p,
     if (rc) return rc;
     HIPCHK(hipSetDevice(c->device));
     const size_t elems = (size_t)q.xres * q.yres * 3;
-    if (elems != c->accum_elems) {
-        if (c->d_accum) hipFree(c->d_accum);
-        c->d_accum = nullptr;
-        c->accum_elems = 0;
-        if (hipMalloc(&c->d_accum, elems * sizeof(float)) != hipSuccess) return fail(c, CR_E_OOM, "accumulator");
-        c->accum_elems = elems;
-        HIPCHK(hipMemset(c->d_accum, 0, elems * sizeof(float)));
-    }
+    if (int r = size_accumulator(c, elems, true)) return r;
     PassTotals sum;
     for (uint32_t done = 0; done < nlayers;) {
         uint32_t m = 1;
@@ -934,13 +773,7 @@ int cr_set_accumulator(cr_ctx *c, uint32_t xres, uint32_t yres, const float *rgb
     if (!rgb || !xres || !yres) return fail(c, CR_E_INVALID, "null / empty accumulator");
     HIPCHK(hipSetDevice(c->device));
     const size_t elems = (size_t)xres * yres * 3;
-    if (elems != c->accum_elems) {
-        if (c->d_accum) hipFree(c->d_accum);
-        c->d_accum = nullptr;
-        c->accum_elems = 0;
-        if (hipMalloc(&c->d_accum, elems * sizeof(float)) != hipSuccess) return fail(c, CR_E_OOM, "accumulator");
-        c->accum_elems = elems;
-    }
+    if (int r = size_accumulator(c, elems, false)) return r;
     HIPCHK(hipMemcpy(c->d_accum, rgb, elems * sizeof(float), hipMemcpyHostToDevice));
     return CR_OK;
 }
@@ -965,10 +798,7 @@ uint32_t cr_layers_per_pass(cr_ctx *c, const cr_render_params *p, uint32_t want)
     const uint64_t items = (uint64_t)cr_tiles_for_rank(p, p->rank) * tile_of(p) * tile_of(p);
     const uint64_t paths_cap = std::min<uint64_t>(c->wf_paths, wf_path_cap(c, p->k));
     uint32_t nl = want;
-    // one chunk of paths, one sample buffer, a 31-bit work index
-    while (nl > 1 && (items * p->spp * nl > paths_cap || items * 12u * p->spp * nl > c->sample_buf ||
-                      items * p->spp * nl >= (1ull << 31)))
-        nl--;
+    while (nl > 1 && !cr::wf_layers_fit(items, p->spp, nl, paths_cap, c->sample_buf)) nl--;
     return nl;
 }
 
@@ -1135,9 +965,7 @@ static int run_query(cr_ctx *c, uint32_t n, bool shadow, const float *orig, cons
     if (e == hipSuccess) e = hipMemcpy(h, c->d_counters, sizeof(h), hipMemcpyDeviceToHost);
     hipFree(buf);
     if (e != hipSuccess) return hip_fail(c, e, "intersect");
-    c->last = cr_counters{h[0], h[1],  h[2],  h[3],  h[4],  h[5],  h[6],  h[7], h[8],
-                          h[9], h[10], h[11], h[12], h[13], h[14], h[15], h[16],
-                          h[17], h[18], h[19], h[20], h[21], h[cr::CTR_NEE]};
+    c->last = counters_of(h);
     return CR_OK;
 }
 

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "leafcull.hpp"
+#include "wfopts.hpp"
 
 namespace cr {
 
@@ -161,9 +162,7 @@ struct RenderArgs {
 };
 // Traversal-stack overflow area of a persistent trace grid of `threads` lanes: [depth][threads] x 8 B.
 inline size_t gstack_bytes(uint32_t depth, uint32_t threads) { return (size_t)depth * threads * 8; }
-// Sample buffer budget: a render is split into sample chunks whose per-sample
-// buffer fits in this many bytes (whole 1080p x 128 spp frames fit in one).
-enum : uint64_t { SAMPLE_BUF_BYTES = 4ull << 30 };
+// (SAMPLE_BUF_BYTES, the sample buffer budget: wfopts.hpp)
 // Per-pixel in-order sum of one chunk's samples; `last` blends / writes the pixel.
 int launch_sum_samples(const RenderArgs &A, bool first, bool last, hipStream_t st, uint32_t lds = 0, bool staged = true);
 
@@ -292,12 +291,7 @@ struct WfKernArgs { // (the same layout as a struct: members in order, each at i
 static_assert(sizeof(RenderArgs) % alignof(RenderArgs) == 0 && alignof(RenderArgs) <= 16 && alignof(WfArgs) <= 16,
               "kernel-argument layout");
 static_assert(offsetof(WfKernArgs, W) == KARG_W && offsetof(WfKernArgs, g) == KARG_G, "kernel-argument layout");
-// rays 2x2 float4, hits 2, shadow ray 2, exclude + occ 8 B, state, (direct, w) pairs, 2 x 2 sort keys + perms,
-// camera sample position, resolve mark
-// spare: + 21 for the queue arrays' spare slots of chunked appends, P / 8 of them at 168 B (cabi.cpp spare_for)
-inline size_t wf_bytes_per_path(int K, bool spare) {
-    return (size_t)(4 + 2 + 2 + WF_STATE + 2 * K) * 16 + 8 + 32 + 8 + 1 + (spare ? 21 : 0);
-}
+// (the arrays of WfArgs inside a chunk's buffer, their sizes and wf_bytes_per_path: wfplan.hpp)
 // Second stream and fork / join events of a render (shadow trace g beside closest trace g + 1).
 struct WfStreams {
     hipStream_t side;

@@ -27,15 +27,11 @@
 #endif
 
 #include "kernels.hpp"
+#include "raysort.hpp" // RS_*, rs_tmp_bytes
 
 namespace cr {
 
 namespace {
-
-constexpr uint32_t RS_BITS = 8, RS_BINS = 1u << RS_BITS;
-constexpr uint32_t RS_THREADS = 256, RS_WAVES = RS_THREADS / 64, RS_ROUNDS = 16;
-constexpr uint32_t RS_TILE = RS_THREADS * RS_ROUNDS; // 4096 pairs
-constexpr uint32_t RS_SEG = RS_THREADS * 16;         // scan segment: 4096 histogram entries
 
 __device__ __forceinline__ uint32_t tile_item(uint32_t wave, uint32_t round, uint32_t lane) {
     return (wave * RS_ROUNDS + round) * 64u + lane;
@@ -211,13 +207,6 @@ __global__ void __launch_bounds__(RS_THREADS) rs_downsweep(const uint32_t *keys_
 }
 
 } // namespace
-
-// Workspace: H [256][ntiles] + segment sums.
-static size_t rs_tmp_bytes(uint32_t n) {
-    const size_t ntiles = (n + RS_TILE - 1) / RS_TILE;
-    const size_t m = RS_BINS * ntiles, nseg = (m + RS_SEG - 1) / RS_SEG;
-    return (m + nseg) * sizeof(uint32_t) + 256;
-}
 
 // keys/vals are double buffers of n entries; returns the index (0/1) of the buffer
 // holding the sorted permutation, or -1 on error.  tmp == nullptr asks for the

@@ -27,6 +27,7 @@
 // queues and the trace waves stay coherent.
 #include "append.hpp"
 #include "camcull.hpp"
+#include "raysort.hpp"
 #include "traverse.hpp"
 
 #include <atomic>
@@ -1719,24 +1720,35 @@ static void launch_shade(const RenderArgs &A, const WfArgs &W, uint32_t g, int n
         hipLaunchKernelGGL(wf_shade<1>, dim3(shade_grid(num_cus, 6)), dim3(256), 0, st, A, W, g);
 }
 
-int launch_wavefront_chunk(const RenderArgs &A, const WfArgs &W0, int num_cus, hipStream_t st, const WfStreams &ss,
-                           TraceEvents *te) {
-    WfArgs W = W0;
-    const WfVariant &v = A.full_counters ? kWfCount
-                         : A.perf_counters ? perf_variant(A.variant)
-                                           : wf_build_or_ref(A.variant);
+// The host side of a chunk's launches, shared by the two chunk drivers below (launch_wavefront_chunk: one
+// chunk, generation by generation; run_wavefront_lanes: two chunks in flight): the render's trace build, the
+// grids, and the launches with their trace events.  A launch that fails leaves its error in err and the
+// launches after it do nothing more than return; the drivers test err after each.
+struct ChunkLauncher {
+    const RenderArgs &A;
+    const int num_cus;
+    TraceEvents *const te;
+    const WfVariant &v;
     uint32_t blk, blocks, tblk, tblocks;
-    wf_trace_geometry(A.full_counters ? -1 : A.variant, num_cus, blk, blocks);
-    const uint32_t cblocks = blocks, sblocks = blocks;
-    wf_tail_geometry(num_cus, tblk, tblocks);
-    if (W.gstride < blk * blocks || W.gstride < tblk * tblocks) return (int)hipErrorInvalidValue;
-    if (blk != 256) return (int)hipErrorInvalidConfiguration; // (wf_trace's per-wave LDS of the leaf exchange)
-    const size_t lds =
-        (size_t)v.ring * blk * sizeof(uint2);
-    const uint32_t sgrid = (uint32_t)(num_cus > 0 ? num_cus : 256) * 8; // grid-stride phases
+    size_t lds;
+    uint32_t sgrid; // grid-stride phases
     int err = 0;
-    // the rest of the chunk from closest queue g on, in one launch
-    auto tail = [&](uint32_t g, hipStream_t s, WfArgs Wt) {
+    ChunkLauncher(const RenderArgs &A_, int num_cus_, TraceEvents *te_)
+        : A(A_), num_cus(num_cus_), te(te_),
+          v(A_.full_counters ? kWfCount : A_.perf_counters ? perf_variant(A_.variant) : wf_build_or_ref(A_.variant)) {
+        wf_trace_geometry(A.full_counters ? -1 : A.variant, num_cus, blk, blocks);
+        wf_tail_geometry(num_cus, tblk, tblocks);
+        lds = (size_t)v.ring * blk * sizeof(uint2);
+        sgrid = (uint32_t)(num_cus > 0 ? num_cus : 256) * 8;
+    }
+    // a chunk whose stack-overflow areas were sized for a grid of gstride threads can run
+    int check(uint32_t gstride) const {
+        if (gstride < blk * blocks || gstride < tblk * tblocks) return (int)hipErrorInvalidValue;
+        if (blk != 256) return (int)hipErrorInvalidConfiguration; // (wf_trace's per-wave LDS of the leaf exchange)
+        return 0;
+    }
+    // the rest of the chunk from closest queue g on, in one launch; the lean build at lean_waves per SIMD
+    void tail(uint32_t g, hipStream_t s, WfArgs Wt, int lean_waves) {
         const size_t tlds = (size_t)8 * tblk * sizeof(uint2);
         Wt.order = nullptr;
         if ((err = trace_event(te, s, TK_TAIL, true))) return;
@@ -1749,32 +1761,49 @@ int launch_wavefront_chunk(const RenderArgs &A, const WfArgs &W0, int num_cus, h
         else if (A.perf_counters)
             hipLaunchKernelGGL((wf_tail<false, 8, TAIL_MINW, 0, true>), dim3(tblocks), dim3(tblk), tlds, s, A, Wt, g);
         else if (v.lc == 5)
-            launch_tail_lean<5>(Wt.tail_waves, tblk, num_cus, tlds, s, A, Wt, g);
+            launch_tail_lean<5>(lean_waves, tblk, num_cus, tlds, s, A, Wt, g);
         else if (v.lc == 4)
-            launch_tail_lean<4>(Wt.tail_waves, tblk, num_cus, tlds, s, A, Wt, g);
+            launch_tail_lean<4>(lean_waves, tblk, num_cus, tlds, s, A, Wt, g);
         else
-            launch_tail_lean<0>(Wt.tail_waves, tblk, num_cus, tlds, s, A, Wt, g);
+            launch_tail_lean<0>(lean_waves, tblk, num_cus, tlds, s, A, Wt, g);
         err = trace_event(te, s, TK_TAIL, false);
-    };
+    }
     // closest trace of generation g on stream s; its stack overflow rows are the
     // second half of gstack when it runs beside a shadow trace
-    auto closest = [&](uint32_t g, hipStream_t s, const uint32_t *order, uint2 *gstack) {
+    void closest(const WfArgs &W, uint32_t g, hipStream_t s, const uint32_t *order, uint2 *gstack) {
         WfArgs Wc = W;
         Wc.order = order;
         Wc.gstack = gstack;
         const int kind = g == 1 ? TK_CAMERA : TK_CLOSEST;
         if ((err = trace_event(te, s, kind, true))) return;
-        hipLaunchKernelGGL(g == 1 ? camera_kernel(v, A) : closest_kernel(v, A, Wc), dim3(g == 1 ? blocks : cblocks),
-                           dim3(blk), lds, s, A, Wc, g);
+        hipLaunchKernelGGL(g == 1 ? camera_kernel(v, A) : closest_kernel(v, A, Wc), dim3(blocks), dim3(blk), lds, s, A,
+                           Wc, g);
         err = trace_event(te, s, kind, false);
-    };
+    }
+    // shadow trace of generation g (Ws: with the queue's order; dead: the queue may hold dead entries), then
+    // wf_resolve of that generation with Wr
+    void shadow_resolve(const WfArgs &Ws, const WfArgs &Wr, uint32_t g, hipStream_t s, bool dead) {
+        if ((err = trace_event(te, s, TK_SHADOW, true))) return;
+        hipLaunchKernelGGL(shadow_kernel(v, A, Ws, dead), dim3(blocks), dim3(blk), lds, s, A, Ws, g);
+        if ((err = trace_event(te, s, TK_SHADOW, false))) return;
+        if (!(Wr.measure_skip & 1u)) hipLaunchKernelGGL(wf_resolve, dim3(sgrid), dim3(256), 0, s, A, Wr, g);
+    }
+};
+
+int launch_wavefront_chunk(const RenderArgs &A, const WfArgs &W0, int num_cus, hipStream_t st, const WfStreams &ss,
+                           TraceEvents *te) {
+    WfArgs W = W0;
+    ChunkLauncher L(A, num_cus, te);
+    if (int e = L.check(W.gstride)) return e;
+    const WfVariant &v = L.v;
+    int &err = L.err;
     W.cam_fused = camera_fuses(v, A, W) ? 1 : 0;
-    if (!W.cam_fused) hipLaunchKernelGGL(wf_camera, dim3(sgrid), dim3(256), 0, st, A, W);
+    if (!W.cam_fused) hipLaunchKernelGGL(wf_camera, dim3(L.sgrid), dim3(256), 0, st, A, W);
     if (W.P < W.tail_min) {
-        tail(1, st, W);
+        L.tail(1, st, W, W.tail_waves);
         return err ? err : (int)hipGetLastError();
     }
-    closest(1, st, nullptr, W.gstack); // camera rays: path order is already coherent
+    L.closest(W, 1, st, nullptr, W.gstack); // camera rays: path order is already coherent
     uint32_t nin = W.P; // rays of closest queue g (generation 1: one per path)
     for (uint32_t g = 1; g <= (uint32_t)A.K && !err; g++) {
         W.app_chunk = v.shadow_dead ? shade_app_chunk(W, nin, num_cus) : 0u;
@@ -1802,27 +1831,25 @@ int launch_wavefront_chunk(const RenderArgs &A, const WfArgs &W0, int num_cus, h
         if (next || overlap) {
             if ((err = (int)hipEventRecord(ss.fork, st)) || (err = (int)hipStreamWaitEvent(ss.side, ss.fork, 0))) break;
             if (next) {
-                closest(g + 1, ss.side, order_c, W.gstack2);
+                L.closest(W, g + 1, ss.side, order_c, W.gstack2);
             } else {
                 WfArgs Wt = W;
                 Wt.gstack = W.gstack2;
                 Wt.tail_shadow_gen = g;
-                tail(g + 1, ss.side, Wt);
+                L.tail(g + 1, ss.side, Wt, W.tail_waves);
             }
             if (err) break;
         }
         W.order = order_s;
         W.ended_only = overlap ? 1u : 0u;
-        if ((err = trace_event(te, st, TK_SHADOW, true))) break;
-        hipLaunchKernelGGL(shadow_kernel(v, A, W, dead), dim3(sblocks), dim3(blk), lds, st, A, W, g);
-        if ((err = trace_event(te, st, TK_SHADOW, false))) break;
-        if (!(W.measure_skip & 1u)) hipLaunchKernelGGL(wf_resolve, dim3(sgrid), dim3(256), 0, st, A, W, g);
+        L.shadow_resolve(W, W, g, st, dead);
+        if (err) break;
         W.ended_only = 0u;
         if (next || overlap)
             if ((err = (int)hipEventRecord(ss.join, ss.side)) || (err = (int)hipStreamWaitEvent(st, ss.join, 0)))
                 break;
         if (!next) {
-            if (nc > 0 && !overlap) tail(g + 1, st, W);
+            if (nc > 0 && !overlap) L.tail(g + 1, st, W, W.tail_waves);
             break;
         }
     }
@@ -1830,56 +1857,21 @@ int launch_wavefront_chunk(const RenderArgs &A, const WfArgs &W0, int num_cus, h
 }
 
 int run_wavefront_lanes(const RenderArgs &A, WfLane *L, int nl, int num_cus, hipStream_t st, TraceEvents *te) {
-    const WfVariant &v = A.full_counters ? kWfCount
-                         : A.perf_counters ? perf_variant(A.variant)
-                                           : wf_build_or_ref(A.variant);
-    uint32_t blk, blocks, tblk, tblocks;
-    wf_trace_geometry(A.full_counters ? -1 : A.variant, num_cus, blk, blocks);
-    const uint32_t cblocks = blocks, sblocks = blocks;
-    wf_tail_geometry(num_cus, tblk, tblocks);
+    ChunkLauncher K(A, num_cus, te);
     for (int i = 0; i < nl; i++)
-        if (L[i].W.gstride < blk * blocks || L[i].W.gstride < tblk * tblocks) return (int)hipErrorInvalidValue;
-    if (blk != 256) return (int)hipErrorInvalidConfiguration; // (wf_trace's per-wave LDS of the leaf exchange)
-    const size_t lds =
-        (size_t)v.ring * blk * sizeof(uint2);
-    const uint32_t sgrid = (uint32_t)(num_cus > 0 ? num_cus : 256) * 8;
-    int err = 0;
+        if (int e = K.check(L[i].W.gstride)) return e;
+    const WfVariant &v = K.v;
+    int &err = K.err;
     struct Run {
         WfArgs W;
         uint32_t g = 0;
         int phase = 0; // 0 idle, 1 shade g, 2 wait for queue lengths of g
         bool past_camera = false;
     } run[2];
-    auto tail = [&](WfLane &ln, WfArgs &W, uint32_t g) {
-        const size_t tlds = (size_t)8 * tblk * sizeof(uint2);
-        W.order = nullptr;
-        if ((err = trace_event(te, ln.st, TK_TAIL, true))) return;
-        if (A.full_counters)
-            hipLaunchKernelGGL((wf_tail<true, 8, TAIL_MINW>), dim3(tblocks), dim3(tblk), tlds, ln.st, A, W, g);
-        else if (A.perf_counters && v.lc == 5)
-            hipLaunchKernelGGL((wf_tail<false, 8, TAIL_MINW, 5, true>), dim3(tblocks), dim3(tblk), tlds, ln.st, A, W, g);
-        else if (A.perf_counters && v.lc == 4)
-            hipLaunchKernelGGL((wf_tail<false, 8, TAIL_MINW, 4, true>), dim3(tblocks), dim3(tblk), tlds, ln.st, A, W, g);
-        else if (A.perf_counters)
-            hipLaunchKernelGGL((wf_tail<false, 8, TAIL_MINW, 0, true>), dim3(tblocks), dim3(tblk), tlds, ln.st, A, W, g);
-        else if (v.lc == 5)
-            hipLaunchKernelGGL((wf_tail<false, 8, TAIL_MINW, 5>), dim3(tblocks), dim3(tblk), tlds, ln.st, A, W, g);
-        else if (v.lc == 4)
-            hipLaunchKernelGGL((wf_tail<false, 8, TAIL_MINW, 4>), dim3(tblocks), dim3(tblk), tlds, ln.st, A, W, g);
-        else
-            hipLaunchKernelGGL((wf_tail<false, 8, TAIL_MINW>), dim3(tblocks), dim3(tblk), tlds, ln.st, A, W, g);
-        err = trace_event(te, ln.st, TK_TAIL, false);
-    };
-    auto closest = [&](const WfArgs &W, uint32_t g, hipStream_t s, const uint32_t *order, uint2 *gstack) {
-        WfArgs Wc = W;
-        Wc.order = order;
-        Wc.gstack = gstack;
-        const int kind = g == 1 ? TK_CAMERA : TK_CLOSEST;
-        if ((err = trace_event(te, s, kind, true))) return;
-        hipLaunchKernelGGL(g == 1 ? camera_kernel(v, A) : closest_kernel(v, A, Wc), dim3(g == 1 ? blocks : cblocks),
-                           dim3(blk), lds, s, A, Wc, g);
-        err = trace_event(te, s, kind, false);
-    };
+    // What this driver does not do, and launch_wavefront_chunk does (kept as it is): its lean tail runs at
+    // TAIL_MINW waves per SIMD whatever "wf_tail_waves" says, generation-1 queues are sorted without consulting
+    // sort_g1, wf_shade never appends in chunks (no dead entries) and the tail is never overlapped.
+    auto tail = [&](WfLane &ln, const WfArgs &W, uint32_t g) { K.tail(g, ln.st, W, TAIL_MINW); };
     auto shade = [&](WfLane &ln, Run &r) { // wf_shade(g), then the queue lengths to the host, async
         launch_shade(A, r.W, r.g, num_cus, ln.st);
         if ((err = (int)hipMemcpyAsync(&ln.hcnt[0], r.W.cnt + WF_G + r.g, 4, hipMemcpyDeviceToHost, ln.st)) ||
@@ -1896,14 +1888,14 @@ int run_wavefront_lanes(const RenderArgs &A, WfLane *L, int nl, int num_cus, hip
         r.past_camera = false;
         if ((err = (int)hipMemsetAsync(r.W.cnt, 0, WF_CNT * sizeof(uint32_t), ln.st))) return;
         r.W.cam_fused = camera_fuses(v, A, r.W) ? 1 : 0;
-        if (!r.W.cam_fused) hipLaunchKernelGGL(wf_camera, dim3(sgrid), dim3(256), 0, ln.st, A, r.W);
+        if (!r.W.cam_fused) hipLaunchKernelGGL(wf_camera, dim3(K.sgrid), dim3(256), 0, ln.st, A, r.W);
         if (P < r.W.tail_min) {
             tail(ln, r.W, 1);
             r.phase = 0;
             r.past_camera = true;
             return;
         }
-        closest(r.W, 1, ln.st, nullptr, r.W.gstack); // camera rays: path order is already coherent
+        K.closest(r.W, 1, ln.st, nullptr, r.W.gstack); // camera rays: path order is already coherent
         if (!err) shade(ln, r);
     };
     // one generation's traces once its queue lengths are on the host; false: not yet
@@ -1925,15 +1917,13 @@ int run_wavefront_lanes(const RenderArgs &A, WfLane *L, int nl, int num_cus, hip
         if (next) {
             if ((err = (int)hipEventRecord(ln.fork, ln.st)) || (err = (int)hipStreamWaitEvent(ln.side, ln.fork, 0)))
                 return true;
-            closest(r.W, g + 1, ln.side, order_c, r.W.gstack2);
+            K.closest(r.W, g + 1, ln.side, order_c, r.W.gstack2);
             if (err) return true;
         }
         WfArgs Ws = r.W;
         Ws.order = order_s;
-        if ((err = trace_event(te, ln.st, TK_SHADOW, true))) return true;
-        hipLaunchKernelGGL(shadow_kernel(v, A, Ws, false), dim3(sblocks), dim3(blk), lds, ln.st, A, Ws, g);
-        if ((err = trace_event(te, ln.st, TK_SHADOW, false))) return true;
-        if (!(r.W.measure_skip & 1u)) hipLaunchKernelGGL(wf_resolve, dim3(sgrid), dim3(256), 0, ln.st, A, r.W, g);
+        K.shadow_resolve(Ws, r.W, g, ln.st, false);
+        if (err) return true;
         if (next) {
             if ((err = (int)hipEventRecord(ln.join, ln.side)) || (err = (int)hipStreamWaitEvent(ln.st, ln.join, 0)))
                 return true;
@@ -1978,10 +1968,7 @@ int run_wavefront_lanes(const RenderArgs &A, WfLane *L, int nl, int num_cus, hip
 
 // Bytes of sort workspace for queues of up to n rays (temp storage only).
 size_t wf_sort_tmp_bytes(uint32_t n, int key_bits) {
-    size_t tb = 0;
-    uint32_t *k[2] = {nullptr, nullptr}, *v[2] = {nullptr, nullptr};
-    sort_queue(k, v, n, key_bits, nullptr, tb, nullptr, false);
-    return tb;
+    return rs_tmp_bytes(n); // (what sort_queue reports for tmp == nullptr, whatever the key width)
 }
 
 } // namespace cr
