@@ -163,6 +163,20 @@ class CrTonemapParams(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("m", "s", "kl", "f", "defog", "gamma")]
 
 
+class CrNoiseParams(C.Structure):
+    """cr_noise_params (include/chiaro_hip.h "noise estimate")."""
+    _fields_ = [("threshold", C.c_float), ("floor", C.c_float)]
+
+
+class CrNoiseStats(C.Structure):
+    """cr_noise_stats: pixels, pixels with err > threshold, the largest err, the layers the frame holds."""
+    _fields_ = [("pixels", C.c_uint64), ("above", C.c_uint64), ("max_err", C.c_float), ("layers", C.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {"pixels": int(self.pixels), "above": int(self.above), "max_err": float(self.max_err),
+                "layers": int(self.layers)}
+
+
 def tonemap_params(exposure, defog=0.0, knee_low=0.0, knee_high=5.0, gamma=2.2) -> CrTonemapParams:
     """cr_tonemap_setup: normalizeImage's host scalars (src/rayTracer.cpp:196-205)."""
     t = CrTonemapParams()
@@ -185,7 +199,9 @@ HIP_SYMBOLS = ("cr_create", "cr_destroy", "cr_last_error", "cr_upload_scene", "c
                "cr_group_rank_ms", "cr_group_ctx", "cr_group_tonemap", "cr_set_accumulator",
                "cr_group_set_accumulator", "cr_layers_per_pass", "cr_render_layers_device",
                "cr_render_tiles_layers_device", "cr_render_layers", "cr_scene_triangles", "cr_layers_per_group",
-               "cr_blend_tiles_layers_device", "cr_render_dist_layers_device", "cr_group_render_layers")
+               "cr_blend_tiles_layers_device", "cr_render_dist_layers_device", "cr_group_render_layers",
+               "cr_noise_struct_sizes", "cr_render_layers_noise_device", "cr_noise_device", "cr_render_layers_noise",
+               "cr_noise", "cr_set_noise_accumulator", "cr_render_until")
 HOST_SYMBOLS = ("chiaro_last_error", "chiaro_scene_create", "chiaro_scene_info_get", "chiaro_scene_destroy",
                 "chiaro_model_create", "chiaro_model_load", "chiaro_model_num_meshes", "chiaro_model_num_triangles",
                 "chiaro_model_num_textures", "chiaro_model_triangles", "chiaro_model_texture",
@@ -201,7 +217,8 @@ HOST_SYMBOLS = ("chiaro_last_error", "chiaro_scene_create", "chiaro_scene_info_g
                 "chiaro_exr_write", "chiaro_exr_write_half", "chiaro_exr_read_half", "chiaro_float_to_half",
                 "chiaro_preview_create", "chiaro_preview_key", "chiaro_preview_mouse", "chiaro_preview_scroll",
                 "chiaro_preview_texture", "chiaro_preview_state", "chiaro_preview_destroy",
-                "chiaro_preview_camera_replay")
+                "chiaro_preview_camera_replay", "chiaro_raytracer_raytrace_until", "chiaro_raytracer_noise",
+                "chiaro_raytracer_noise_map", "chiaro_noise_struct_sizes")
 
 P = C.c_void_p
 FP = C.POINTER(C.c_float)
@@ -294,6 +311,17 @@ def libs():
     _sig(hip, "cr_group_set_accumulator", C.c_int, [P, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)])
     _sig(hip, "cr_group_tonemap", C.c_int, [P, C.POINTER(CrTonemapParams), C.c_uint32, C.c_uint32,
                                             C.POINTER(C.c_uint8)])
+    NP, NS = C.POINTER(CrNoiseParams), C.POINTER(CrNoiseStats)
+    _sig(hip, "cr_noise_struct_sizes", None, [UP, UP])
+    _sig(hip, "cr_render_layers_noise_device", C.c_int,
+         [P, C.POINTER(CrCamera), C.POINTER(CrRenderParams), C.c_uint32, P, P, P])
+    _sig(hip, "cr_noise_device", C.c_int, [P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, NP, P, P, P, P, P])
+    _sig(hip, "cr_render_layers_noise", C.c_int,
+         [P, C.POINTER(CrCamera), C.POINTER(CrRenderParams), C.c_uint32, FP, FP])
+    _sig(hip, "cr_noise", C.c_int, [P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, NP, FP, NS])
+    _sig(hip, "cr_set_noise_accumulator", C.c_int, [P, C.c_uint32, C.c_uint32, FP])
+    _sig(hip, "cr_render_until", C.c_int, [P, C.POINTER(CrCamera), C.POINTER(CrRenderParams), C.c_uint32, C.c_uint32,
+                                           C.c_uint32, NP, C.c_uint64, FP, NS])
 
     _sig(host, "chiaro_last_error", C.c_char_p, [])
     _sig(host, "chiaro_scene_create", P, [C.c_int, C.POINTER(C.c_char_p)])
@@ -317,6 +345,11 @@ def libs():
     _sig(host, "chiaro_raytracer_create", P, [P, P, C.c_int])
     _sig(host, "chiaro_raytracer_raytrace", C.c_int, [P, FP, FP, FP, C.c_float])
     _sig(host, "chiaro_raytracer_raytrace_layers", C.c_int, [P, C.c_uint32, FP, FP, FP, C.c_float])
+    _sig(host, "chiaro_raytracer_raytrace_until", C.c_int, [P, C.c_float, C.c_uint32, FP, FP, FP, C.c_float, C.c_float,
+                                                            C.c_uint32, C.c_uint64, UP])
+    _sig(host, "chiaro_raytracer_noise", C.c_int, [P, NS])
+    _sig(host, "chiaro_raytracer_noise_map", C.c_int, [P, FP])
+    _sig(host, "chiaro_noise_struct_sizes", None, [UP, UP])
     _sig(host, "chiaro_raytracer_pixels", FP, [P])
     _sig(host, "chiaro_raytracer_data", C.POINTER(C.c_uint8), [P])
     _sig(host, "chiaro_raytracer_maxval", C.c_float, [P])
@@ -530,6 +563,65 @@ class Device:
         self._chk(libs()[0].cr_render_layers(self._c, C.byref(cam), C.byref(p), nlayers, _ptr(out)),
                   "cr_render_layers")
         return out
+
+    def render_layers_noise(self, cam: CrCamera, p: CrRenderParams, nlayers: int, accum: np.ndarray | None = None,
+                            m2: np.ndarray | None = None):
+        """cr_render_layers_noise: render_layers that also blends the layers into the ctx's moment accumulator;
+        returns (frame, m2), both [yres][xres][3]."""
+        out = accum if accum is not None else np.zeros((p.yres, p.xres, 3), np.float32)
+        mom = m2 if m2 is not None else np.zeros((p.yres, p.xres, 3), np.float32)
+        for a in (out, mom):
+            assert a.dtype == np.float32 and a.flags.c_contiguous and a.size == p.yres * p.xres * 3
+        self._chk(libs()[0].cr_render_layers_noise(self._c, C.byref(cam), C.byref(p), int(nlayers), _ptr(out),
+                                                   _ptr(mom)), "cr_render_layers_noise")
+        return out, mom
+
+    def render_layers_noise_device(self, cam, p, nlayers: int, d_frame_ptr: int, d_m2_ptr: int, stream: int = 0):
+        """cr_render_layers_noise_device: render_layers_device that also blends the layers' second moments into
+        the device moment frame d_m2 [yres][xres][3]."""
+        self._chk(libs()[0].cr_render_layers_noise_device(self._c, C.byref(cam), C.byref(p), int(nlayers),
+                                                          C.c_void_p(d_frame_ptr), C.c_void_p(d_m2_ptr),
+                                                          C.c_void_p(stream)), "cr_render_layers_noise_device")
+
+    def noise_device(self, xres: int, yres: int, layers: int, spp: int, threshold: float, floor: float,
+                     d_frame_ptr: int, d_m2_ptr: int, d_err_ptr: int, d_stats_ptr: int, stream: int = 0):
+        """cr_noise_device: the error map (d_err [yres][xres], 0: none) and the statistic (d_stats: 24 bytes of
+        device memory laid out as CrNoiseStats) of a device frame and moment frame, enqueued on `stream`."""
+        np_ = CrNoiseParams(float(threshold), float(floor))
+        self._chk(libs()[0].cr_noise_device(self._c, int(xres), int(yres), int(layers), int(spp), C.byref(np_),
+                                            C.c_void_p(d_frame_ptr), C.c_void_p(d_m2_ptr),
+                                            C.c_void_p(d_err_ptr or None), C.c_void_p(d_stats_ptr),
+                                            C.c_void_p(stream)), "cr_noise_device")
+
+    def noise(self, xres: int, yres: int, layers: int, spp: int, threshold: float, floor: float,
+              want_err: bool = True):
+        """cr_noise on the ctx's two accumulators: (stats dict, error map [yres][xres] or None)."""
+        np_ = CrNoiseParams(float(threshold), float(floor))
+        st = CrNoiseStats()
+        err = np.zeros((yres, xres), np.float32) if want_err else None
+        self._chk(libs()[0].cr_noise(self._c, int(xres), int(yres), int(layers), int(spp), C.byref(np_),
+                                     _ptr(err) if want_err else None, C.byref(st)), "cr_noise")
+        return st.as_dict(), err
+
+    def set_noise_accumulator(self, m2: np.ndarray):
+        """cr_set_noise_accumulator: the ctx's moment accumulator becomes m2 [yres][xres][3]."""
+        m2 = np.ascontiguousarray(m2, np.float32)
+        self._chk(libs()[0].cr_set_noise_accumulator(self._c, m2.shape[1], m2.shape[0], _ptr(m2)),
+                  "cr_set_noise_accumulator")
+
+    def render_until(self, cam: CrCamera, p: CrRenderParams, min_layers: int, max_layers: int, check_every: int,
+                     threshold: float, floor: float, max_above: int = 0, accum: np.ndarray | None = None):
+        """cr_render_until: layers from p.layer in pass groups of at most check_every, the noise checked after
+        each, until layers >= min_layers and at most max_above pixels are above threshold, or max_layers;
+        returns (frame, stats dict) -- stats["layers"] is the last layer rendered."""
+        out = accum if accum is not None else np.zeros((p.yres, p.xres, 3), np.float32)
+        assert out.dtype == np.float32 and out.flags.c_contiguous and out.size == p.yres * p.xres * 3
+        np_ = CrNoiseParams(float(threshold), float(floor))
+        st = CrNoiseStats()
+        self._chk(libs()[0].cr_render_until(self._c, C.byref(cam), C.byref(p), int(min_layers), int(max_layers),
+                                            int(check_every), C.byref(np_), int(max_above), _ptr(out), C.byref(st)),
+                  "cr_render_until")
+        return out, st.as_dict()
 
     def render_device(self, cam, p, d_frame_ptr: int, stream: int = 0):
         self._chk(libs()[0].cr_render_device(self._c, C.byref(cam), C.byref(p), C.c_void_p(d_frame_ptr),
@@ -850,6 +942,29 @@ class RayTracer:
         rc = libs()[1].chiaro_raytracer_raytrace_layers(self._h, int(n), _fa(eye), _fa(center), _fa(up), float(yview))
         if rc:
             raise RuntimeError("rayTraceLayers: " + _host_err())
+
+    def rayTraceUntil(self, threshold, maxLayers, eye, center, up=(0.0, 1.0, 0.0), yview=1.0, floor=1e-3,
+                      checkEvery=4, maxAbove=0) -> int:
+        """rayTrace calls with the same view until at most maxAbove pixels have a relative error above
+        threshold, or maxLayers; returns the layer reached (lastNoise() tells whether the target was met)."""
+        reached = C.c_uint32(0)
+        rc = libs()[1].chiaro_raytracer_raytrace_until(self._h, float(threshold), int(maxLayers), _fa(eye),
+                                                       _fa(center), _fa(up), float(yview), float(floor),
+                                                       int(checkEvery), int(maxAbove), C.byref(reached))
+        if rc:
+            raise RuntimeError("rayTraceUntil: " + _host_err())
+        return int(reached.value)
+
+    def lastNoise(self) -> dict:
+        st = CrNoiseStats()
+        libs()[1].chiaro_raytracer_noise(self._h, C.byref(st))
+        return st.as_dict()
+
+    def noiseMap(self) -> np.ndarray:
+        err = np.zeros((self.yres, self.xres), np.float32)
+        if libs()[1].chiaro_raytracer_noise_map(self._h, _ptr(err)):
+            raise RuntimeError("noiseMap: " + _host_err())
+        return err
 
     @property
     def pixels(self) -> np.ndarray:

@@ -193,8 +193,9 @@ cr_counters counters_of(const unsigned long long *h) {
 }
 
 int run_render(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, float *out, int mode, hipStream_t st,
-               uint32_t nl, uint32_t piece_k, uint32_t piece_m, uint64_t stride) {
+               uint32_t nl, uint32_t piece_k, uint32_t piece_m, uint64_t stride, float *m2) {
     if (!cam || !out) return fail(c, CR_E_INVALID, "null camera/output");
+    if (m2 && mode != cr::MODE_BLEND) return fail(c, CR_E_INVALID, "moments are tracked for blended frames only");
     int rc = check_params(c, p);
     if (rc) return rc;
     if (nl < 1 || (nl > 1 && (c->kernel != 2 || c->wf_lanes != 1)))
@@ -233,6 +234,8 @@ int run_render(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, float
     if (int r = grow(c, &c->d_samples, c->samples_bytes, pl.samples_bytes)) return r;
     if (pl.chunked)
         if (int r = grow(c, &c->d_run, c->run_bytes, pl.run_bytes)) return r;
+    if (pl.chunked && m2)
+        if (int r = grow(c, &c->d_run2, c->run2_bytes, pl.run_bytes)) return r;
     if (int r = grow(c, &c->d_wf, c->wf_bytes, pl.need_alloc)) return r;
     if (lanes == 2)
         if (int r = grow(c, &c->d_wf2, c->wf2_bytes, pl.need_alloc)) return r;
@@ -280,7 +283,8 @@ int run_render(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, float
             }
             W.P = P;
         }
-        if (!e) e = cr::launch_sum_samples(A, s0 == 0, s0 + A.s_count == pl.spp_pass, st, c->sum_lds, c->sum_staged != 0);
+        if (!e) e = cr::launch_sum_samples(A, s0 == 0, s0 + A.s_count == pl.spp_pass, st, c->sum_lds, c->sum_staged != 0,
+                                            m2, (float *)c->d_run2);
         if (e) return hip_fail(c, (hipError_t)e, "render kernel launch");
     }
     HIPCHK(hipEventRecord(c->ev1, st));
@@ -365,6 +369,10 @@ void cr_destroy(cr_ctx *c) {
         if (c->d_gstack) hipFree(c->d_gstack);
         if (c->d_samples) hipFree(c->d_samples);
         if (c->d_run) hipFree(c->d_run);
+        if (c->d_accum2) hipFree(c->d_accum2);
+        if (c->d_run2) hipFree(c->d_run2);
+        if (c->d_err) hipFree(c->d_err);
+        if (c->d_nstats) hipFree(c->d_nstats);
         if (c->d_wf) hipFree(c->d_wf);
         if (c->d_cull) hipFree(c->d_cull);
         if (c->d_cull_node) hipFree(c->d_cull_node);
@@ -679,6 +687,17 @@ static int size_accumulator(cr_ctx *c, size_t elems, bool zero) {
     if (zero) HIPCHK(hipMemset(c->d_accum, 0, elems * sizeof(float)));
     return CR_OK;
 }
+// ... and the moment accumulator beside it (cr_render_layers_noise, cr_render_until, cr_set_noise_accumulator)
+static int size_noise_accumulator(cr_ctx *c, size_t elems, bool zero) {
+    if (elems == c->accum2_elems) return CR_OK;
+    if (c->d_accum2) hipFree(c->d_accum2);
+    c->d_accum2 = nullptr;
+    c->accum2_elems = 0;
+    if (hipMalloc(&c->d_accum2, elems * sizeof(float)) != hipSuccess) return fail(c, CR_E_OOM, "moment accumulator");
+    c->accum2_elems = elems;
+    if (zero) HIPCHK(hipMemset(c->d_accum2, 0, elems * sizeof(float)));
+    return CR_OK;
+}
 
 int cr_render(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, float *accum_rgb_out) {
     if (!c) return CR_E_INVALID;
@@ -727,6 +746,34 @@ uint32_t crx::group_layers(cr_ctx *c, const cr_render_params *p, uint32_t want, 
         }
     return 1;
 }
+// One pass group of the whole frame (g.nranks 1) blended into the ctx's accumulator: as many of `want` layers
+// from g.layer (at most LAYER_GROUP) as fit, in the fewest frame pieces whose paths fit one chunk; m2: the ctx's
+// moment accumulator takes the same layers.  *nl_out: the layers rendered; the passes' counters and times are
+// added to `sum`.
+static int render_layer_group(cr_ctx *c, const cr_camera *cam, const cr_render_params &g, uint32_t want, float *m2,
+                              crx::PassTotals &sum, uint32_t *nl_out) {
+    uint32_t m = 1;
+    const uint32_t nl = crx::group_layers(c, &g, std::min(LAYER_GROUP, want), &m);
+    for (uint32_t k = 0; k < m; k++) {
+        cr_render_params t = g;
+        t.rank = k;
+        t.nranks = m;
+        if (int rc = crx::run_render(c, cam, &t, c->d_accum, cr::MODE_BLEND, c->stream, nl, 0, 1, 0, m2)) return rc;
+        sum.add(c);
+    }
+    *nl_out = nl;
+    return CR_OK;
+}
+// Layers q.layer .. + nlayers - 1 in pass groups
+static int render_layer_groups(cr_ctx *c, const cr_camera *cam, const cr_render_params &q, uint32_t nlayers, float *m2,
+                               crx::PassTotals &sum) {
+    for (uint32_t done = 0, nl = 0; done < nlayers; done += nl) {
+        cr_render_params g = q;
+        g.layer = q.layer + done;
+        if (int rc = render_layer_group(c, cam, g, nlayers - done, m2, sum, &nl)) return rc;
+    }
+    return CR_OK;
+}
 extern "C" {
 
 uint32_t cr_layers_per_group(cr_ctx *c, const cr_render_params *p, uint32_t want) {
@@ -749,19 +796,7 @@ int cr_render_layers(cr_ctx *c, const cr_camera *cam, const cr_render_params *p,
     const size_t elems = (size_t)q.xres * q.yres * 3;
     if (int r = size_accumulator(c, elems, true)) return r;
     PassTotals sum;
-    for (uint32_t done = 0; done < nlayers;) {
-        uint32_t m = 1;
-        const uint32_t nl = group_layers(c, &q, std::min(LAYER_GROUP, nlayers - done), &m);
-        for (uint32_t k = 0; k < m; k++) {
-            cr_render_params t = q;
-            t.layer = q.layer + done;
-            t.rank = k;
-            t.nranks = m;
-            if ((rc = run_render(c, cam, &t, c->d_accum, cr::MODE_BLEND, c->stream, nl))) return rc;
-            sum.add(c);
-        }
-        done += nl;
-    }
+    if ((rc = render_layer_groups(c, cam, q, nlayers, nullptr, sum))) return rc;
     sum.store(c);
     HIPCHK(hipMemcpy(accum_rgb_out, c->d_accum, elems * sizeof(float), hipMemcpyDeviceToHost));
     return CR_OK;
@@ -775,6 +810,166 @@ int cr_set_accumulator(cr_ctx *c, uint32_t xres, uint32_t yres, const float *rgb
     const size_t elems = (size_t)xres * yres * 3;
     if (int r = size_accumulator(c, elems, false)) return r;
     HIPCHK(hipMemcpy(c->d_accum, rgb, elems * sizeof(float), hipMemcpyHostToDevice));
+    return CR_OK;
+}
+
+// ---- noise estimate.  The new entry points check their arguments first, then the device,
+// then the scene: a null pointer is CR_E_INVALID with or without a GPU.
+} // extern "C"
+static int check_noise_params(cr_ctx *c, const cr_noise_params *np) {
+    if (!np) return fail(c, CR_E_INVALID, "null noise params");
+    if (!(np->floor > 0.f) || std::isinf(np->floor)) return fail(c, CR_E_INVALID, "noise floor must be > 0 and finite");
+    if (!(np->threshold >= 0.f)) return fail(c, CR_E_INVALID, "noise threshold must be >= 0");
+    return CR_OK;
+}
+static int check_noise_shape(cr_ctx *c, uint32_t xres, uint32_t yres, uint32_t layers, uint32_t spp) {
+    if (!xres || !yres || !layers || !spp) return fail(c, CR_E_INVALID, "xres/yres/layers/spp must be > 0");
+    if ((uint64_t)xres * yres > (1ull << 31)) return fail(c, CR_E_INVALID, "image too large");
+    if ((uint64_t)layers * spp > 0xFFFFFFFFull) return fail(c, CR_E_INVALID, "layers * spp must fit 32 bits");
+    return CR_OK;
+}
+// zero the device statistic and evaluate (frame, m2) on st; nothing waits for it here
+static int enqueue_noise(cr_ctx *c, uint32_t xres, uint32_t yres, uint32_t layers, uint32_t spp,
+                         const cr_noise_params *np, const float *d_frame, const float *d_m2, float *d_err,
+                         cr_noise_stats *d_stats, hipStream_t st) {
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemsetAsync(d_stats, 0, sizeof(cr_noise_stats), st));
+    cr::NoiseArgs N{};
+    N.frame = d_frame;
+    N.m2 = d_m2;
+    N.err = d_err;
+    N.stats = d_stats;
+    N.npix = xres * yres;
+    N.layers = layers;
+    N.n = (float)(layers * spp);
+    N.threshold = np->threshold;
+    N.floor = np->floor;
+    if (int e = cr::launch_noise_eval(N, st)) return hip_fail(c, (hipError_t)e, "noise kernel launch");
+    return CR_OK;
+}
+// the ctx's two accumulators evaluated on its stream, the statistic (and the error map) copied to the host
+static int noise_of_accumulators(cr_ctx *c, uint32_t xres, uint32_t yres, uint32_t layers, uint32_t spp,
+                                 const cr_noise_params *np, float *err_out, cr_noise_stats *stats_out) {
+    const size_t npix = (size_t)xres * yres;
+    if (c->accum_elems != 3 * npix || c->accum2_elems != 3 * npix || !c->d_accum || !c->d_accum2)
+        return fail(c, CR_E_INVALID, "cr_noise: no frame and moment accumulator of this size (render with "
+                                     "cr_render_layers_noise / cr_render_until first)");
+    if (int r = grow(c, &c->d_nstats, c->nstats_bytes, sizeof(cr_noise_stats))) return r;
+    if (err_out)
+        if (int r = grow(c, &c->d_err, c->err_bytes, npix * sizeof(float))) return r;
+    if (int r = enqueue_noise(c, xres, yres, layers, spp, np, c->d_accum, c->d_accum2,
+                              err_out ? (float *)c->d_err : nullptr, (cr_noise_stats *)c->d_nstats, c->stream))
+        return r;
+    HIPCHK(hipMemcpyAsync(stats_out, c->d_nstats, sizeof(cr_noise_stats), hipMemcpyDeviceToHost, c->stream));
+    if (err_out) HIPCHK(hipMemcpyAsync(err_out, c->d_err, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return CR_OK;
+}
+extern "C" {
+
+void cr_noise_struct_sizes(uint32_t *params_bytes, uint32_t *stats_bytes) {
+    if (params_bytes) *params_bytes = (uint32_t)sizeof(cr_noise_params);
+    if (stats_bytes) *stats_bytes = (uint32_t)sizeof(cr_noise_stats);
+}
+
+int cr_render_layers_noise_device(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, uint32_t nlayers,
+                                  float *d_frame, float *d_m2, void *stream) {
+    if (!c) return CR_E_INVALID;
+    if (!cam || !p || !d_frame || !d_m2 || nlayers < 1)
+        return fail(c, CR_E_INVALID, "null camera/params/frame/moment frame or no layers");
+    if (c->device < 0) return fail(c, CR_E_HIP, c->err.empty() ? "no device" : c->err);
+    return run_render(c, cam, p, d_frame, cr::MODE_BLEND, (hipStream_t)stream, nlayers, 0, 1, 0, d_m2);
+}
+
+int cr_noise_device(cr_ctx *c, uint32_t xres, uint32_t yres, uint32_t layers, uint32_t spp, const cr_noise_params *np,
+                    const float *d_frame, const float *d_m2, float *d_err, cr_noise_stats *d_stats, void *stream) {
+    if (!c) return CR_E_INVALID;
+    if (!d_frame || !d_m2 || !d_stats) return fail(c, CR_E_INVALID, "null frame / moment frame / stats");
+    if (int r = check_noise_params(c, np)) return r;
+    if (int r = check_noise_shape(c, xres, yres, layers, spp)) return r;
+    if (c->device < 0) return fail(c, CR_E_HIP, c->err.empty() ? "no device" : c->err);
+    return enqueue_noise(c, xres, yres, layers, spp, np, d_frame, d_m2, d_err, d_stats, (hipStream_t)stream);
+}
+
+int cr_render_layers_noise(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, uint32_t nlayers,
+                           float *accum_rgb_out, float *m2_out) {
+    if (!c) return CR_E_INVALID;
+    if (!cam || !p || !accum_rgb_out || nlayers < 1)
+        return fail(c, CR_E_INVALID, "null camera/params/output or no layers");
+    if (c->device < 0) return fail(c, CR_E_HIP, c->err.empty() ? "no device" : c->err);
+    cr_render_params q = *p;
+    if (q.nranks == 0) q.nranks = 1;
+    if (q.nranks != 1) return fail(c, CR_E_INVALID, "cr_render_layers_noise: the whole frame (nranks 1)");
+    int rc = check_params(c, &q);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    const size_t elems = (size_t)q.xres * q.yres * 3;
+    if (int r = size_accumulator(c, elems, true)) return r;
+    if (int r = size_noise_accumulator(c, elems, true)) return r;
+    PassTotals sum;
+    if ((rc = render_layer_groups(c, cam, q, nlayers, c->d_accum2, sum))) return rc;
+    sum.store(c);
+    HIPCHK(hipMemcpy(accum_rgb_out, c->d_accum, elems * sizeof(float), hipMemcpyDeviceToHost));
+    if (m2_out) HIPCHK(hipMemcpy(m2_out, c->d_accum2, elems * sizeof(float), hipMemcpyDeviceToHost));
+    return CR_OK;
+}
+
+int cr_noise(cr_ctx *c, uint32_t xres, uint32_t yres, uint32_t layers, uint32_t spp, const cr_noise_params *np,
+             float *err_out, cr_noise_stats *stats_out) {
+    if (!c) return CR_E_INVALID;
+    if (!stats_out) return fail(c, CR_E_INVALID, "null stats");
+    if (int r = check_noise_params(c, np)) return r;
+    if (int r = check_noise_shape(c, xres, yres, layers, spp)) return r;
+    if (c->device < 0) return fail(c, CR_E_HIP, c->err.empty() ? "no device" : c->err);
+    return noise_of_accumulators(c, xres, yres, layers, spp, np, err_out, stats_out);
+}
+
+int cr_set_noise_accumulator(cr_ctx *c, uint32_t xres, uint32_t yres, const float *m2) {
+    if (!c) return CR_E_INVALID;
+    if (!m2 || !xres || !yres) return fail(c, CR_E_INVALID, "null / empty moment accumulator");
+    if (c->device < 0) return fail(c, CR_E_HIP, c->err.empty() ? "no device" : c->err);
+    HIPCHK(hipSetDevice(c->device));
+    const size_t elems = (size_t)xres * yres * 3;
+    if (int r = size_noise_accumulator(c, elems, false)) return r;
+    HIPCHK(hipMemcpy(c->d_accum2, m2, elems * sizeof(float), hipMemcpyHostToDevice));
+    return CR_OK;
+}
+
+int cr_render_until(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, uint32_t min_layers,
+                    uint32_t max_layers, uint32_t check_every, const cr_noise_params *np, uint64_t max_above,
+                    float *accum_rgb_out, cr_noise_stats *stats_out) {
+    if (!c) return CR_E_INVALID;
+    if (!cam || !p || !accum_rgb_out || !stats_out) return fail(c, CR_E_INVALID, "null camera/params/output/stats");
+    if (int r = check_noise_params(c, np)) return r;
+    if (check_every < 1 || p->layer < 1 || max_layers < p->layer)
+        return fail(c, CR_E_INVALID, "cr_render_until: check_every >= 1 and 1 <= p->layer <= max_layers");
+    if (c->device < 0) return fail(c, CR_E_HIP, c->err.empty() ? "no device" : c->err);
+    cr_render_params q = *p;
+    if (q.nranks == 0) q.nranks = 1;
+    if (q.nranks != 1) return fail(c, CR_E_INVALID, "cr_render_until: the whole frame (nranks 1)");
+    int rc = check_params(c, &q);
+    if (rc) return rc;
+    if ((rc = check_noise_shape(c, q.xres, q.yres, max_layers, q.spp))) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    const size_t elems = (size_t)q.xres * q.yres * 3;
+    if (int r = size_accumulator(c, elems, true)) return r;
+    if (int r = size_noise_accumulator(c, elems, true)) return r;
+    PassTotals sum;
+    cr_noise_stats st{};
+    // one pass group of at most check_every layers (fewer when fewer fit a group), then a check
+    for (uint32_t layer = q.layer - 1; layer < max_layers;) {
+        uint32_t n = 0;
+        cr_render_params g = q;
+        g.layer = layer + 1;
+        if ((rc = render_layer_group(c, cam, g, std::min(check_every, max_layers - layer), c->d_accum2, sum, &n)))
+            return rc;
+        layer += n;
+        if ((rc = noise_of_accumulators(c, q.xres, q.yres, layer, q.spp, np, nullptr, &st))) return rc;
+        if (layer >= min_layers && st.above <= max_above) break;
+    }
+    sum.store(c);
+    HIPCHK(hipMemcpy(accum_rgb_out, c->d_accum, elems * sizeof(float), hipMemcpyDeviceToHost));
+    *stats_out = st;
     return CR_OK;
 }
 

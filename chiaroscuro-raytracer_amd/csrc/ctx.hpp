@@ -48,6 +48,13 @@ struct cr_ctx : cr::WfOptions {
     size_t accum_elems = 0;
     void *d_gstack = nullptr, *d_samples = nullptr, *d_run = nullptr, *d_wf = nullptr;
     size_t gstack_bytes = 0, samples_bytes = 0, run_bytes = 0, wf_bytes = 0;
+    // noise estimate (cr_render_layers_noise / cr_noise / cr_render_until): the moment accumulator beside
+    // d_accum, the squares' running sum beside d_run (sample-chunked passes), the error map and the device
+    // statistic of cr_noise -- all grow-only, freed in cr_destroy
+    float *d_accum2 = nullptr;
+    size_t accum2_elems = 0;
+    void *d_run2 = nullptr, *d_err = nullptr, *d_nstats = nullptr;
+    size_t run2_bytes = 0, err_bytes = 0, nstats_bytes = 0;
     void *d_cull = nullptr;  // camera-ray cull boxes, one per leaf reference (+ 4), per render
     size_t cull_bytes = 0;
     void *d_cull_node = nullptr; // ... their per-leaf unions, one per kd node
@@ -124,8 +131,10 @@ int grow(cr_ctx *c, void **buf, size_t &cap, size_t need);
 // nl > 1 (wavefront kernel): layers p->layer .. p->layer + nl - 1 in one pass (cr_render_layers_device)
 // piece_m > 1 (MODE_TILES): p is piece piece_k of a rank's tiles (rank r + piece_k * N of an
 // N * piece_m split), written into the rank's compact buffer of layer stride `stride` floats
+// m2 (MODE_BLEND): the layers' second moments are blended into this moment frame beside `out`
 int run_render(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, float *out, int mode, hipStream_t st,
-               uint32_t nl = 1, uint32_t piece_k = 0, uint32_t piece_m = 1, uint64_t stride = 0);
+               uint32_t nl = 1, uint32_t piece_k = 0, uint32_t piece_m = 1, uint64_t stride = 0,
+               float *m2 = nullptr);
 // group.cpp: the communicator and buffers of the multi-process split (cr_destroy)
 void release_dist(cr_ctx *c);
 // The largest nl <= want (>= 1) whose paths fit one chunk when p's share (the frame for nranks 1, else rank

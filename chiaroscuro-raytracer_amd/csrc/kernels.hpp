@@ -164,7 +164,22 @@ struct RenderArgs {
 inline size_t gstack_bytes(uint32_t depth, uint32_t threads) { return (size_t)depth * threads * 8; }
 // (SAMPLE_BUF_BYTES, the sample buffer budget: wfopts.hpp)
 // Per-pixel in-order sum of one chunk's samples; `last` blends / writes the pixel.
-int launch_sum_samples(const RenderArgs &A, bool first, bool last, hipStream_t st, uint32_t lds = 0, bool staged = true);
+// m2 (MODE_BLEND only): also blend the layers' second moments into the moment frame m2 [yres][xres][3], the
+// squares' running sum carried across sample chunks in run2 [n_items][3] (samples.hip; both pointers are the
+// sum kernels' own arguments -- RenderArgs, which the trace kernels read by offset, stays as it is)
+int launch_sum_samples(const RenderArgs &A, bool first, bool last, hipStream_t st, uint32_t lds = 0, bool staged = true,
+                       float *m2 = nullptr, float *run2 = nullptr);
+
+// noise.hip: the per-pixel error of a frame against its moment frame and the frame statistic
+// (cr_noise_device).  stats: the device cr_noise_stats, zeroed on the stream before the launch.
+struct NoiseArgs {
+    const float *frame, *m2; // [npix][3]
+    float *err;              // [npix] or null
+    void *stats;             // cr_noise_stats (device)
+    uint32_t npix, layers;
+    float n, threshold, floor; // n = (float)(layers * spp)
+};
+int launch_noise_eval(const NoiseArgs &N, hipStream_t st);
 
 // Wavefront path tracer (wavefront.hip, cr_set_option "kernel" 2): the paths of
 // work items [w0, w0 + P) advance one bounce per generation through separate

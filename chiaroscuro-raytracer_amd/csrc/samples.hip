@@ -7,33 +7,71 @@
 
 namespace cr {
 
+// The moment frame's blend of one layer (MODE_BLEND): q, the in-order sum of the layer's squared samples, blended
+// into m2 [yres][xres][3] exactly as write_pixel blends the radiance sum into the frame (rayTracer.cpp:64).
+__device__ __forceinline__ void write_moment(const RenderArgs &A, float *m2, uint32_t x, uint32_t y, f3 q,
+                                             uint32_t lj) {
+    const float inv = 1.f / (float)A.spp;
+    const uint32_t layer = A.layer + lj;
+    float *o = m2 + 3 * ((size_t)y * A.xres + x);
+    const f3 old = (layer > 1) ? mk(o[0], o[1], o[2]) : mk(0.f, 0.f, 0.f);
+    const f3 nw = divs(add(muls(old, (float)(layer - 1)), muls(q, inv)), (float)layer);
+    o[0] = nw.x;
+    o[1] = nw.y;
+    o[2] = nw.z;
+}
+
 // Per pixel: add this launch's samples in sample order onto the running sum
 // (A.run, carried across sample chunks), then on the last chunk blend the
 // layer into the frame / write the tile mean (write_pixel).
-__global__ void __launch_bounds__(256) sum_samples(RenderArgs A, int first, int last) {
+// M2 (cr_render_layers_noise_device, MODE_BLEND): a second accumulator takes each sample's square (the product
+// rounded, then added, in the same order; carried across sample chunks in run2) and is blended into the moment
+// frame m2 wherever the sum is blended into the frame.  Without M2 the two pointers are unused and the
+// kernel's operations are the ones it always had.
+template <bool M2>
+__global__ void __launch_bounds__(256) sum_samples(RenderArgs A, int first, int last, float *m2, float *run2) {
     const uint32_t item = blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t px = 0, py = 0;
     const bool valid = item < A.n_items && item_pixel(A, item, px, py);
     if (valid) {
         f3 temp = mk(0.f, 0.f, 0.f);
         if (!first) temp = mk(A.run[3 * (size_t)item], A.run[3 * (size_t)item + 1], A.run[3 * (size_t)item + 2]);
+        f3 sq = mk(0.f, 0.f, 0.f);
+        if (M2 && !first) sq = mk(run2[3 * (size_t)item], run2[3 * (size_t)item + 1], run2[3 * (size_t)item + 2]);
         const float *sm = A.samples + 3 * (size_t)item * A.s_count;
         // A.nl layers in one pass (never sample-chunked): each layer's run of A.spp samples is
         // summed in sample order and blended / written as its own layer, in layer order
         for (uint32_t j = 0; j + 1 < A.nl; j++) {
-            for (uint32_t s = j * A.spp; s < (j + 1) * A.spp; s++)
-                temp = add(temp, mk(sm[3 * s], sm[3 * s + 1], sm[3 * s + 2]));
+            for (uint32_t s = j * A.spp; s < (j + 1) * A.spp; s++) {
+                const f3 v = mk(sm[3 * s], sm[3 * s + 1], sm[3 * s + 2]);
+                temp = add(temp, v);
+                if (M2) sq = add(sq, mul(v, v));
+            }
             write_pixel(A, px, py, item, temp, j);
             temp = mk(0.f, 0.f, 0.f);
+            if (M2) {
+                write_moment(A, m2, px, py, sq, j);
+                sq = mk(0.f, 0.f, 0.f);
+            }
         }
         const uint32_t s_first = (A.nl - 1) * A.spp;
-        for (uint32_t s = s_first; s < A.s_count; s++) temp = add(temp, mk(sm[3 * s], sm[3 * s + 1], sm[3 * s + 2]));
+        for (uint32_t s = s_first; s < A.s_count; s++) {
+            const f3 v = mk(sm[3 * s], sm[3 * s + 1], sm[3 * s + 2]);
+            temp = add(temp, v);
+            if (M2) sq = add(sq, mul(v, v));
+        }
         if (last) {
             write_pixel(A, px, py, item, temp, A.nl - 1);
+            if (M2) write_moment(A, m2, px, py, sq, A.nl - 1);
         } else {
             A.run[3 * (size_t)item] = temp.x;
             A.run[3 * (size_t)item + 1] = temp.y;
             A.run[3 * (size_t)item + 2] = temp.z;
+            if (M2) {
+                run2[3 * (size_t)item] = sq.x;
+                run2[3 * (size_t)item + 1] = sq.y;
+                run2[3 * (size_t)item + 2] = sq.z;
+            }
         }
     }
     const uint64_t b = __ballot(valid && last);
@@ -48,7 +86,8 @@ __global__ void __launch_bounds__(256) sum_samples(RenderArgs A, int first, int 
 // waves streaming beside it have evicted it from L2 (2-3x the sample bytes at the fabric).  Needs
 // s_count % 4 == 0 (16-B aligned runs).
 enum : uint32_t { SUM_C = 16, SUM_ROW = 3 * SUM_C + 1 }; // (+1: the rows of consecutive pixels start in other banks)
-__global__ void __launch_bounds__(256) sum_samples_lds(RenderArgs A, int first, int last) {
+template <bool M2>
+__global__ void __launch_bounds__(256) sum_samples_lds(RenderArgs A, int first, int last, float *m2, float *run2) {
     __shared__ float buf[256 * SUM_ROW];
     const uint32_t item0 = blockIdx.x * blockDim.x, item = item0 + threadIdx.x;
     const uint32_t nitems = min((uint32_t)blockDim.x, A.n_items - item0);
@@ -56,6 +95,8 @@ __global__ void __launch_bounds__(256) sum_samples_lds(RenderArgs A, int first, 
     const bool valid = item < A.n_items && item_pixel(A, item, px, py);
     f3 temp = mk(0.f, 0.f, 0.f);
     if (valid && !first) temp = mk(A.run[3 * (size_t)item], A.run[3 * (size_t)item + 1], A.run[3 * (size_t)item + 2]);
+    f3 sq = mk(0.f, 0.f, 0.f); // (M2: the squares' sum, fed from the same staged values)
+    if (M2 && valid && !first) sq = mk(run2[3 * (size_t)item], run2[3 * (size_t)item + 1], run2[3 * (size_t)item + 2]);
     const uint32_t S = A.s_count;
     const float4 *run4 = (const float4 *)(A.samples + 3 * (size_t)item0 * S); // S % 4 == 0: 16-B aligned
     const size_t stride4 = 3 * (size_t)S / 4;                                   // float4 per pixel run
@@ -76,12 +117,18 @@ __global__ void __launch_bounds__(256) sum_samples_lds(RenderArgs A, int first, 
         if (valid) {
             const float *b = buf + threadIdx.x * SUM_ROW;
             for (uint32_t t = 0; t < cs; t++) {
-                temp = add(temp, mk(b[3 * t], b[3 * t + 1], b[3 * t + 2]));
+                const f3 v = mk(b[3 * t], b[3 * t + 1], b[3 * t + 2]);
+                temp = add(temp, v);
+                if (M2) sq = add(sq, mul(v, v));
                 // A.nl layers in one pass (never sample-chunked): a layer's run ends -> blend / write it
                 const uint32_t s = s0 + t + 1;
                 if (A.nl > 1 && s < S && s % A.spp == 0) {
                     write_pixel(A, px, py, item, temp, lj);
                     temp = mk(0.f, 0.f, 0.f);
+                    if (M2) {
+                        write_moment(A, m2, px, py, sq, lj);
+                        sq = mk(0.f, 0.f, 0.f);
+                    }
                     lj++;
                 }
             }
@@ -90,10 +137,16 @@ __global__ void __launch_bounds__(256) sum_samples_lds(RenderArgs A, int first, 
     if (valid) {
         if (last) {
             write_pixel(A, px, py, item, temp, A.nl - 1);
+            if (M2) write_moment(A, m2, px, py, sq, A.nl - 1);
         } else {
             A.run[3 * (size_t)item] = temp.x;
             A.run[3 * (size_t)item + 1] = temp.y;
             A.run[3 * (size_t)item + 2] = temp.z;
+            if (M2) {
+                run2[3 * (size_t)item] = sq.x;
+                run2[3 * (size_t)item + 1] = sq.y;
+                run2[3 * (size_t)item + 2] = sq.z;
+            }
         }
     }
     const uint64_t bl = __ballot(valid && last);
@@ -103,13 +156,22 @@ __global__ void __launch_bounds__(256) sum_samples_lds(RenderArgs A, int first, 
 // lds: dynamic LDS reserved per block (unused: it only caps the blocks per CU, so fewer waves share
 // each CU's slice of L2 while they stream their pixels' sample runs; option "sum_lds")
 // staged: sum_samples_lds when the runs are 16-B aligned (option "sum_staged", default)
-int launch_sum_samples(const RenderArgs &A, bool first, bool last, hipStream_t st, uint32_t lds, bool staged) {
+// m2: the moment-tracking instantiations (MODE_BLEND), blending into the moment frame m2; run2 carries the
+// squares' running sum across sample chunks ([n_items][3], as A.run); null: the plain kernels
+int launch_sum_samples(const RenderArgs &A, bool first, bool last, hipStream_t st, uint32_t lds, bool staged,
+                       float *m2, float *run2) {
     const uint32_t blocks = (A.n_items + 255) / 256;
     if (!blocks) return (int)hipGetLastError();
-    if (staged && A.s_count % 4 == 0)
-        hipLaunchKernelGGL(sum_samples_lds, dim3(blocks), dim3(256), lds, st, A, first ? 1 : 0, last ? 1 : 0);
+    const int f = first ? 1 : 0, l = last ? 1 : 0;
+    const bool lds_kernel = staged && A.s_count % 4 == 0;
+    if (m2 && lds_kernel)
+        hipLaunchKernelGGL(sum_samples_lds<true>, dim3(blocks), dim3(256), lds, st, A, f, l, m2, run2);
+    else if (m2)
+        hipLaunchKernelGGL(sum_samples<true>, dim3(blocks), dim3(256), lds, st, A, f, l, m2, run2);
+    else if (lds_kernel)
+        hipLaunchKernelGGL(sum_samples_lds<false>, dim3(blocks), dim3(256), lds, st, A, f, l, m2, run2);
     else
-        hipLaunchKernelGGL(sum_samples, dim3(blocks), dim3(256), lds, st, A, first ? 1 : 0, last ? 1 : 0);
+        hipLaunchKernelGGL(sum_samples<false>, dim3(blocks), dim3(256), lds, st, A, f, l, m2, run2);
     return (int)hipGetLastError();
 }
 

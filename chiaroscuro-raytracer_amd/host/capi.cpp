@@ -279,6 +279,41 @@ int chiaro_raytracer_raytrace_layers(chiaro_raytracer *r, uint32_t n, const floa
         CR_E_HIP);
 }
 
+int chiaro_raytracer_raytrace_until(chiaro_raytracer *r, float threshold, uint32_t max_layers, const float eye[3],
+                                    const float center[3], const float up[3], float yview, float floor,
+                                    uint32_t check_every, uint64_t max_above, uint32_t *layer_out) {
+    if (!r || !eye || !center || !up) return CR_E_INVALID;
+    return guard(
+        [&]() -> int {
+            const unsigned reached =
+                r->r->rayTraceUntil(threshold, max_layers, vec3(eye[0], eye[1], eye[2]),
+                                    vec3(center[0], center[1], center[2]), vec3(up[0], up[1], up[2]), yview, floor,
+                                    check_every, max_above);
+            if (layer_out) *layer_out = reached;
+            return CR_OK;
+        },
+        CR_E_HIP);
+}
+int chiaro_raytracer_noise(const chiaro_raytracer *r, cr_noise_stats *out) {
+    if (!r || !out) return CR_E_INVALID;
+    *out = r->r->lastNoise();
+    return CR_OK;
+}
+int chiaro_raytracer_noise_map(chiaro_raytracer *r, float *err_out) {
+    if (!r || !err_out) return CR_E_INVALID;
+    return guard(
+        [&]() -> int {
+            const std::vector<float> e = r->r->noiseMap();
+            std::memcpy(err_out, e.data(), e.size() * sizeof(float));
+            return CR_OK;
+        },
+        CR_E_HIP);
+}
+void chiaro_noise_struct_sizes(uint32_t *params_bytes, uint32_t *stats_bytes) {
+    if (params_bytes) *params_bytes = (uint32_t)sizeof(cr_noise_params);
+    if (stats_bytes) *stats_bytes = (uint32_t)sizeof(cr_noise_stats);
+}
+
 const float *chiaro_raytracer_pixels(const chiaro_raytracer *r) { return r ? r->r->pixelData() : nullptr; }
 const uint8_t *chiaro_raytracer_data(chiaro_raytracer *r) { return r ? r->r->getData() : nullptr; }
 float chiaro_raytracer_maxval(const chiaro_raytracer *r) { return r ? r->r->maxVal : 0.f; }

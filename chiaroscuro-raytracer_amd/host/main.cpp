@@ -10,6 +10,8 @@
 // Extra token "layers N" (this build): render N progressive layers of the same
 // view (the reference's preview accumulates them the same way,
 // src/rayTracer.cpp:17-33, src/openglPreview.cpp:247-255).
+// Extra token "noise T" (this build): render until no pixel's relative error exceeds T
+// (RayTracer::rayTraceUntil); N of "layers N" is then the most layers to render.
 #include "model.hpp"
 #include "raytracer.hpp"
 #include "scene.hpp"
@@ -24,10 +26,19 @@
 int main(int argc, char **argv) {
     // strip this build's own tokens before Scene sees them
     unsigned layers = 1;
+    float noise = -1.f; // "noise T": T >= 0
     std::vector<char *> args;
     for (int i = 0; i < argc; i++) {
         if (i > 1 && !std::strcmp(argv[i], "layers") && i + 1 < argc) {
             layers = (unsigned)std::max(1, std::atoi(argv[++i]));
+            continue;
+        }
+        if (i > 1 && !std::strcmp(argv[i], "noise") && i + 1 < argc) {
+            noise = (float)std::atof(argv[++i]);
+            if (!(noise >= 0.f)) {
+                std::fprintf(stderr, "chiaroscuro: noise takes a threshold >= 0\n");
+                return 1;
+            }
             continue;
         }
         args.push_back(argv[i]);
@@ -40,7 +51,14 @@ int main(int argc, char **argv) {
         if (!model.error.empty()) std::fprintf(stderr, "%s\n", model.error.c_str());
         chiaro::RayTracer renderer(model, scene);
         // the layers in pass groups (RayTracer::rayTraceLayers, bit-identical to one rayTrace per layer)
-        renderer.rayTraceLayers(layers, scene.VP, scene.LA, scene.UP, scene.yview);
+        if (noise >= 0.f) {
+            const unsigned reached = renderer.rayTraceUntil(noise, layers, scene.VP, scene.LA, scene.UP, scene.yview);
+            const cr_noise_stats &st = renderer.lastNoise();
+            std::fprintf(stderr, "noise %g: layer %u of at most %u reached, %llu of %llu pixels above, max error %g (%s)\n",
+                         noise, reached, layers, (unsigned long long)st.above, (unsigned long long)st.pixels,
+                         st.max_err, st.above == 0 ? "converged" : "not converged");
+        } else
+            renderer.rayTraceLayers(layers, scene.VP, scene.LA, scene.UP, scene.yview);
         std::fprintf(stderr, "layers 1..%u: %.3f s, %llu rays\n", renderer.layers(), renderer.lastSeconds(),
                      (unsigned long long)(renderer.lastCounters().closest + renderer.lastCounters().shadow));
         renderer.exportImage(scene.renderPath.c_str());

@@ -105,6 +105,7 @@ void RayTracer::rayTrace(vec3 eye, vec3 center, vec3 up, float yview) { rayTrace
 
 void RayTracer::rayTraceLayers(unsigned n, vec3 eye, vec3 center, vec3 up, float yview) {
     if (n < 1) return;
+    noiseTracked_ = false; // (these layers keep no moments: a later rayTraceUntil starts over)
     // rayTracer.cpp:24 -- including the reference's `(lastUp == lastUp)`: a
     // change of `up` alone does not reset the accumulation.
     const bool newLayer = (eye == lastEye) && (center == lastCenter) && (lastUp == lastUp) && (yview == lastYview);
@@ -171,6 +172,64 @@ void RayTracer::rayTraceLayers(unsigned n, vec3 eye, vec3 center, vec3 up, float
     if (!std::getenv("CHIARO_QUIET")) std::cerr << "took " << lastSeconds_ << " seconds.\n";
 }
 
+unsigned RayTracer::rayTraceUntil(float threshold, unsigned maxLayers, vec3 eye, vec3 center, vec3 up, float yview,
+                                  float floor, unsigned checkEvery, uint64_t maxAbove) {
+    if (group_) throw std::runtime_error("chiaro: rayTraceUntil renders on one GPU (gpus 1)");
+    if (maxLayers < 1) throw std::runtime_error("chiaro: rayTraceUntil: maxLayers must be >= 1");
+    // rayTraceLayers' rule (rayTracer.cpp:24), and the frame's moments must be complete to go on with it
+    const bool newLayer = noiseTracked_ && (eye == lastEye) && (center == lastCenter) && (lastUp == lastUp) &&
+                          (yview == lastYview);
+    if (newLayer && layers_ >= maxLayers) return layers_;
+    const unsigned first = newLayer ? layers_ + 1 : 1;
+    if (!newLayer) {
+        lastEye = eye;
+        lastCenter = center;
+        lastUp = up;
+        lastYview = yview;
+    }
+    const auto t0 = std::chrono::high_resolution_clock::now();
+    const cr_camera cam = make_camera(eye, center, up, yview, scene.xres, scene.yres);
+    cr_render_params p{};
+    p.xres = scene.xres;
+    p.yres = scene.yres;
+    p.spp = scene.samples;
+    p.k = scene.k;
+    p.background[0] = scene.background.x;
+    p.background[1] = scene.background.y;
+    p.background[2] = scene.background.z;
+    p.seed = scene.seed;
+    p.layer = first;
+    p.rank = 0;
+    p.nranks = 1;
+    p.tile = 32;
+    const cr_noise_params np{threshold, floor};
+    cr_noise_stats st{};
+    if (cr_render_until(ctx_, &cam, &p, 1, maxLayers, checkEvery, &np, maxAbove, pixels.data(), &st) != CR_OK) {
+        // (the accumulators may hold any number of this call's layers: the next render starts over)
+        layers_ = 0;
+        noiseTracked_ = false;
+        throw std::runtime_error(std::string("chiaro: render failed: ") + cr_last_error(ctx_));
+    }
+    layers_ = st.layers;
+    noiseTracked_ = true;
+    noise_ = st;
+    noiseParams_ = np;
+    cr_get_counters(ctx_, &counters_);
+    maxVal = 0.f;
+    for (float v : pixels) maxVal = maxVal > v ? maxVal : v;
+    lastSeconds_ = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
+    return layers_;
+}
+
+std::vector<float> RayTracer::noiseMap() {
+    if (!noiseTracked_) throw std::runtime_error("chiaro: noiseMap: the frame is not a rayTraceUntil render");
+    std::vector<float> err((size_t)scene.xres * scene.yres);
+    cr_noise_stats st{};
+    if (cr_noise(ctx_, scene.xres, scene.yres, layers_, scene.samples, &noiseParams_, err.data(), &st) != CR_OK)
+        throw std::runtime_error(std::string("chiaro: noise map failed: ") + cr_last_error(ctx_));
+    return err;
+}
+
 uint8_t *RayTracer::getData() { return data.data(); }
 
 void RayTracer::saveCheckpoint(const char *path) const {
@@ -212,6 +271,7 @@ void RayTracer::resume(const char *path) {
     if (rc != CR_OK)
         throw std::runtime_error(std::string("resume: ") + (group_ ? cr_group_last_error(group_) : cr_last_error(ctx_)));
     layers_ = h.layers;
+    noiseTracked_ = false; // (the checkpoint holds the frame only)
     lastEye = vec3(h.eye[0], h.eye[1], h.eye[2]);
     lastCenter = vec3(h.center[0], h.center[1], h.center[2]);
     lastUp = vec3(h.up[0], h.up[1], h.up[2]);

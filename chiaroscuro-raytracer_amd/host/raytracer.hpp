@@ -36,6 +36,19 @@ class RayTracer {
      * (cr_render_layers / cr_group_render_layers with the `gpus` key: several layers per pass group,
      * bit-identical). */
     void rayTraceLayers(unsigned n, vec3 eye, vec3 center, vec3 up = vec3(0.f, 1.f, 0.f), float yview = 1.f);
+    /* This build: rayTrace calls with the same view until the frame is quiet enough (cr_render_until): layers
+     * are added, the noise checked after each pass group of at most checkEvery layers, until at most maxAbove
+     * pixels have a relative error above threshold (include/chiaro_hip.h "noise estimate") or the frame holds
+     * maxLayers layers.  The progressive state follows rayTraceLayers' rules: the same view continues the
+     * accumulation -- when rayTraceUntil rendered every layer of it, so the moments are complete (a frame that
+     * already holds maxLayers is left as it is) -- and anything else starts at layer 1; a later rayTrace /
+     * rayTraceLayers continues the frame as usual.  Returns the layer reached; lastNoise() tells whether the
+     * target was met.  One GPU only: with gpus > 1 it throws std::runtime_error. */
+    unsigned rayTraceUntil(float threshold, unsigned maxLayers, vec3 eye, vec3 center, vec3 up = vec3(0.f, 1.f, 0.f),
+                           float yview = 1.f, float floor = 1e-3f, unsigned checkEvery = 4, uint64_t maxAbove = 0);
+    /* The statistic of the last rayTraceUntil's last check, and the error map [yres][xres] of its frame. */
+    const cr_noise_stats &lastNoise() const { return noise_; }
+    std::vector<float> noiseMap();
     /* Get RGB (24 bits per pixel) image location. */
     uint8_t *getData();
     /* The biggest single pixel color generated in last rayTrace() call. */
@@ -67,6 +80,9 @@ class RayTracer {
     cr_ctx *ctx_ = nullptr;
     cr_group *group_ = nullptr;
     cr_counters counters_{};
+    cr_noise_stats noise_{};
+    cr_noise_params noiseParams_{0.f, 0.f}; // of the last rayTraceUntil (floor 0: none yet)
+    bool noiseTracked_ = false;             // every layer of the frame came from rayTraceUntil (moments complete)
     double lastSeconds_ = 0.0;
     // rayTracer.cpp:18-22 progressive-layer state (per instance here, not function-static)
     unsigned layers_ = 0;

@@ -34,6 +34,11 @@
  *   cr_comm_* / cr_render_dist_device
  *                        the same split with one process per GPU (RCCL
  *                        communicator from a unique id the caller distributes).
+ *   cr_render_layers_noise / cr_render_layers_noise_device / cr_noise / cr_noise_device / cr_render_until
+ *                        the progressive accumulation (src/rayTracer.cpp:18-33) and its per-pixel
+ *                        sample loop and blend (:59-64) with a second-moment frame kept beside the
+ *                        frame, a per-pixel error from the two, and a render that stops at a noise
+ *                        target (no reference counterpart: its callers fix the layer count).
  *   cr_intersect         KDTree::intersectRay       (src/kdtree.cpp:210-216)
  *   cr_intersect_shadow  KDTree::intersectShadowRay (src/kdtree.cpp:283-290)
  *   cr_intersect_device / cr_intersect_shadow_device
@@ -259,6 +264,72 @@ uint32_t cr_scene_triangles(cr_ctx *ctx);
  * row-major tile slots; with nranks > 1 each tile row is rotated by its index, so a
  * rank's tiles spread over every column class). */
 int cr_tile_origin(const cr_render_params *p, uint32_t rank, uint32_t local, uint32_t *x0, uint32_t *y0);
+
+/* ------------------------------------------------------ noise estimate --
+ * How noisy the progressive frame still is, and a render that stops when it is quiet enough.  The reference
+ * accumulates layers until its caller stops asking (src/rayTracer.cpp:18-33, the blend at :59-64) and keeps no
+ * measure of what the frame has converged to; a caller cannot add one, because the per-sample radiances exist
+ * only inside a render pass.  A noise render keeps a second frame, the MOMENT FRAME m2 [yres][xres][3], beside
+ * the frame: per pixel and layer q = the sum over the layer's samples, in sample order, of the sample's
+ * radiance squared per channel (the product rounded, then added), blended exactly as the frame is,
+ *   m2 = (m2 * (L-1) + q * (1/spp)) / L        (layer 1: the old value counts as 0)
+ * so m2 is the running mean of the squared samples as the frame is the running mean of the samples, and both
+ * are defined bit for bit (float32, no contraction, IEEE / and sqrt).
+ * The error of a pixel, with mean = the frame, n = (float)(layers * spp) and the caller's floor > 0:
+ *   per channel  v = m2 - mean * mean;  v = v > 0 ? v : 0 (a NaN too);  se = sqrt(v / n)
+ *   err = ((se_r + se_g) + se_b) / (((mean_r + mean_g) + mean_b) + floor)       (a NaN err counts as 0)
+ * -- the standard error of the pixel's mean relative to its brightness.  The frame statistic: `pixels`, `above`
+ * = the pixels with err > threshold, `max_err` = the largest err (0 when none is positive); counts and a maximum
+ * do not depend on the order of a reduction, so they are exact.  m2 - mean^2 cancels in float32: the estimate
+ * bottoms out near sqrt(2^-24 / n) relative, and thresholds below about 1e-3 are not meaningful.
+ * Errors: a null pointer, floor <= 0 (or not finite), a NaN or negative threshold: CR_E_INVALID (checked first);
+ * no device: CR_E_HIP; no scene: CR_E_NOSCENE.
+ * Not covered: tile means (cr_render_tiles_*), cr_group_*, cr_comm_* and the distributed renders keep no moment
+ * frame (a second tile buffer would have to be gathered over RCCL).  The checkpoint file holds the frame only:
+ * a resumed render starts a new noise history unless the caller saved m2 and restores it
+ * (cr_set_noise_accumulator). */
+typedef struct cr_noise_params {
+    float threshold; /* a pixel counts in `above` when err > threshold (>= 0) */
+    float floor;     /* added to the brightness the error is relative to (> 0): black pixels stay finite */
+} cr_noise_params;
+typedef struct cr_noise_stats {
+    uint64_t pixels;  /* xres * yres */
+    uint64_t above;   /* pixels with err > threshold */
+    float max_err;    /* largest err of the frame */
+    uint32_t layers;  /* the layers the frame holds (cr_render_until: the last layer rendered) */
+} cr_noise_stats;
+/* sizeof the two structures as this library was built (for FFI callers to check their mirrors) */
+void cr_noise_struct_sizes(uint32_t *params_bytes, uint32_t *stats_bytes);
+/* cr_render_layers_device that also blends layers p->layer .. + nlayers - 1 into the caller's device moment
+ * frame d_m2 [yres][xres][3] (nlayers 1 allowed; with p->nranks > 1 the rank's tiles of both frames, blended in
+ * place, as cr_render_layers cuts a frame into pieces).  The frame's bits are cr_render_layers_device's.  For
+ * layer 1 the old contents of both frames are ignored. */
+int cr_render_layers_noise_device(cr_ctx *ctx, const cr_camera *cam, const cr_render_params *p, uint32_t nlayers,
+                                  float *d_frame, float *d_m2, void *stream);
+/* The error map and statistic of (d_frame, d_m2) holding `layers` layers of spp samples, stream-ordered on
+ * `stream` without a host synchronisation: *d_stats (device memory) is zeroed and filled, `layers` written
+ * through; d_err [yres][xres] may be null.  Needs no scene. */
+int cr_noise_device(cr_ctx *ctx, uint32_t xres, uint32_t yres, uint32_t layers, uint32_t spp,
+                    const cr_noise_params *np, const float *d_frame, const float *d_m2, float *d_err,
+                    cr_noise_stats *d_stats, void *stream);
+/* cr_render_layers that also blends the layers into the ctx's moment accumulator (grow-only, beside the
+ * frame's); m2_out [yres][xres][3] may be null.  Bit-identical frame. */
+int cr_render_layers_noise(cr_ctx *ctx, const cr_camera *cam, const cr_render_params *p, uint32_t nlayers,
+                           float *accum_rgb_out, float *m2_out);
+/* The error map (err_out [yres][xres], may be null) and statistic of the ctx's two accumulators. */
+int cr_noise(cr_ctx *ctx, uint32_t xres, uint32_t yres, uint32_t layers, uint32_t spp, const cr_noise_params *np,
+             float *err_out, cr_noise_stats *stats_out);
+/* cr_set_accumulator's sibling for the moment accumulator: a caller that saved m2 resumes its noise history. */
+int cr_set_noise_accumulator(cr_ctx *ctx, uint32_t xres, uint32_t yres, const float *m2);
+/* Render until quiet: from layer p->layer (whole frame, p->nranks 1) one pass group of at most check_every
+ * layers at a time (fewer when fewer fit a group, cr_layers_per_group), the noise evaluated after each group;
+ * stops at the first check with stats.layers >= min_layers and stats.above <= max_above, or at layer max_layers
+ * (>= p->layer).  stats_out->layers is the last layer rendered -- the caller reads convergence from
+ * above <= max_above.  The frame is bit-identical to cr_render_layers of the same layers; counters,
+ * cr_last_kernel_ms and the trace stats sum over the groups. */
+int cr_render_until(cr_ctx *ctx, const cr_camera *cam, const cr_render_params *p, uint32_t min_layers,
+                    uint32_t max_layers, uint32_t check_every, const cr_noise_params *np, uint64_t max_above,
+                    float *accum_rgb_out, cr_noise_stats *stats_out);
 
 /* Ray queries (host arrays). dir need not be normalised (the reference does not). */
 int cr_intersect(cr_ctx *ctx, uint32_t n, const float *orig, const float *dir, uint32_t *hit, uint32_t *tri,

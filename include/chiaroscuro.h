@@ -8,6 +8,9 @@
  *   chiaro_raytracer_create  RayTracer::RayTracer(Model&, Scene&)  src/rayTracer.cpp:13-15
  *                            (builds KDTree, src/kdtree.cpp:34-108, uploads via cr_upload_scene)
  *   chiaro_raytracer_raytrace RayTracer::rayTrace                  src/rayTracer.cpp:17-74
+ *   chiaro_raytracer_raytrace_until / _noise / _noise_map
+ *                            rayTrace repeated until a noise target is met (this build; the accumulation of
+ *                            src/rayTracer.cpp:18-33,59-64 with a second-moment frame, cr_render_until)
  *   chiaro_raytracer_data / _maxval / _normalize / _export
  *                            getData / maxVal / normalizeImage / exportImage (rayTracer.cpp:171-279)
  *   chiaro_camera            the camera basis of rayTrace          src/rayTracer.cpp:41-49
@@ -81,6 +84,20 @@ int chiaro_raytracer_raytrace(chiaro_raytracer *r, const float eye[3], const flo
  * GPU (cr_render_layers) or across the `gpus` group (cr_group_render_layers); bit-identical. */
 int chiaro_raytracer_raytrace_layers(chiaro_raytracer *r, uint32_t n, const float eye[3], const float center[3],
                                      const float up[3], float yview);
+/* RayTracer::rayTraceUntil: rayTrace calls with the same view (the accumulation of src/rayTracer.cpp:18-33,59-64)
+ * until at most max_above pixels have a relative error above threshold or the frame holds max_layers layers;
+ * the noise is checked after each pass group of at most check_every layers (cr_render_until, include/chiaro_hip.h
+ * "noise estimate"; floor > 0 is added to the brightness the error is relative to, 1e-3 a usual value).
+ * *layer_out (may be NULL): the layer reached.  One GPU only (the `gpus` key above 1: an error).
+ * chiaro_raytracer_noise: the statistic of the last check; chiaro_raytracer_noise_map: the error map
+ * [yres][xres] of that frame.  chiaro_noise_struct_sizes: sizeof cr_noise_params / cr_noise_stats as this
+ * library was built. */
+int chiaro_raytracer_raytrace_until(chiaro_raytracer *r, float threshold, uint32_t max_layers, const float eye[3],
+                                    const float center[3], const float up[3], float yview, float floor,
+                                    uint32_t check_every, uint64_t max_above, uint32_t *layer_out);
+int chiaro_raytracer_noise(const chiaro_raytracer *r, cr_noise_stats *out);
+int chiaro_raytracer_noise_map(chiaro_raytracer *r, float *err_out);
+void chiaro_noise_struct_sizes(uint32_t *params_bytes, uint32_t *stats_bytes);
 const float *chiaro_raytracer_pixels(const chiaro_raytracer *r);
 const uint8_t *chiaro_raytracer_data(chiaro_raytracer *r);
 float chiaro_raytracer_maxval(const chiaro_raytracer *r);
