@@ -75,12 +75,11 @@ int grow(cr_ctx *c, void **buf, size_t &cap, size_t need) {
     return CR_OK;
 }
 
-// scenes with fewer triangles default to trace build 18 instead of 26 (fill_args)
-const uint32_t LEAF_CULL_MIN_TRIS = 65536;
-using cr::SORT_MIN_TRIS; // (wfplan.hpp: scenes below it trace their queues in append order)
+using cr::LEAF_CULL_MIN_TRIS; // (wfbuilds.hpp: scenes below it default to the build without the leaf cull)
+using cr::SORT_MIN_TRIS;      // (wfplan.hpp: scenes below it trace their queues in append order)
 
-// The scene's default trace build: 59 from LEAF_CULL_MIN_TRIS triangles on, else 44 (the history: fill_args).
-int default_trace_build(const cr_ctx *c) { return c->n_tris >= LEAF_CULL_MIN_TRIS ? 59 : 44; }
+// The scene's default trace build (wfbuilds.hpp wf_default_build; the history: fill_args).
+int default_trace_build(const cr_ctx *c) { return cr::wf_default_build(c->n_tris); }
 
 // What every launch of the trace kernels takes from the ctx's options and the scene's size, a render's
 // (fill_args) and a device query's (run_query_device) alike.
@@ -138,8 +137,9 @@ void fill_args(cr_ctx *c, cr::RenderArgs &A, const cr_camera *cam, const cr_rend
     A.diag_kinds = c->diag_kinds;
     A.lc_debug = c->lc_debug;
     fill_trace_tuning(c, A);
-    // wavefront trace builds (wavefront.hip kWf): 2 = LDS ring 8, 8 waves/SIMD, scalar loads for
-    // wave-uniform nodes / leaves: 1003 vs 935 Mray/s for the same build without them (variant 1);
+    // The history of the wavefront trace builds (the ones there are: wfbuilds.hpp kWfBuilds; most of the numbers
+    // below are measured and removed).  2 = LDS ring 8, 8 waves/SIMD, scalar loads for
+    // wave-uniform nodes / leaves: 1003 vs 935 Mray/s for the same build without them (build 1);
     // 6 = 2 + fat node records (a node and both children in 32 B: one dependent load per two
     // descent levels): 595.0 vs 597.5 ms per 1080p x 128 spp pass, 83.0 vs 84.2 ms for rank 0 of 8;
     // 9 = 6 with branch-light descent steps and uniform-leaf tests (fewer scalar-unit exec-mask
@@ -215,8 +215,8 @@ int run_render(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, float
         return fail(c, CR_E_INVALID, "trace build " + std::to_string(A.variant) +
                                          " does not exist (DESIGN.md §3 lists the measured builds that were removed)");
     if (c->perf_counters && (c->kernel != 2 || c->full_counters || !cr::wf_perf_available(A.variant)))
-        return fail(c, CR_E_INVALID, "perf_counters: the wavefront kernel's trace builds 18, 26, 40, 42, 43, 44, "
-                                     "49, 53, 54 and 59 only, without the counting build");
+        return fail(c, CR_E_INVALID, "perf_counters: the wavefront kernel's trace builds " + cr::wf_perf_builds_text() +
+                                         " only, without the counting build");
     c->last_build = c->kernel == 2 ? (c->full_counters ? -1 : A.variant) : -2;
     HIPCHK(hipMemsetAsync(c->d_counters, 0, cr::CTR_SLOTS * sizeof(unsigned long long), st));
     uint32_t blk, blocks;
@@ -1204,7 +1204,7 @@ size_t carve_query(const cr_ctx *c, uint32_t cap, bool trace, int variant, char 
     if (!trace) return off;
     uint32_t blk = 0, blocks = 0, blk44 = 0, blocks44 = 0;
     cr::wf_trace_geometry(variant, c->num_cus, blk, blocks);
-    cr::wf_trace_geometry(44, c->num_cus, blk44, blocks44);
+    cr::wf_trace_geometry(cr::WF_BUILD_QUERY_FAT, c->num_cus, blk44, blocks44);
     B.gstride = std::max(blk * blocks, blk44 * blocks44);
     B.qc = (uint32_t *)take(cr::QC_N * sizeof(uint32_t));
     B.cnt = (uint32_t *)take(cr::WF_CNT * sizeof(uint32_t));

@@ -64,7 +64,8 @@ struct cr_ctx : cr::WfOptions {
     cr_trace_stats last_trace{};
     // options
     // Defaults from sweeps on MI355X, sponza stand-in 1080p x 128 spp:
-    //   wavefront (kernel 2), trace variant 9, refill 64/56/48, sorted queues, tail below 1M rays
+    //   wavefront (kernel 2), the scene's default trace build (wfbuilds.hpp wf_default_build), refill 64/56/48,
+    //   sorted queues, tail below 1M rays
     //   (the persistent megakernel, kernel 0: 615 Mray/s; one thread per pixel, kernel 1: ~60; both removed)
     int kernel = 2;
     int full_counters = 1;

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "leafcull.hpp"
+#include "wfbuilds.hpp"
 #include "wfopts.hpp"
 
 namespace cr {
@@ -137,7 +138,7 @@ struct RenderArgs {
     uint32_t gstride;             // threads in the persistent trace grid
     int full_counters;            // 1: also count inner/leaf/tritest (SURVEY §8d bytes)
     int perf_counters;            // 1: the default build's kernels with performed-work counts (CTR_PERF)
-    int variant;                  // wavefront trace build (wavefront.hip kWf)
+    int variant;                  // wavefront trace build (wfbuilds.hpp kWfBuilds)
     uint32_t refill;              // idle lanes of a wave that trigger a path-state step / ray fetch
     uint32_t refill_shadow;       // wavefront shadow-trace kernel's threshold
     uint32_t refill_camera;       // wavefront closest trace of generation 1 (camera rays)
@@ -312,23 +313,16 @@ struct WfStreams {
     hipStream_t side;
     hipEvent_t fork, join;
 };
-int num_wf_variants();
+// (the trace builds, their availability, cull and geometry lookups -- wf_variant_available, wf_variant_culls,
+// wf_variant_leaf_cull, wf_perf_available, num_wf_variants, wf_trace_geometry: wfbuilds.hpp)
 // the most blocks a chunked-append wf_shade launch has at the ctx's wf_shade_waves (spare-slot sizing)
 uint32_t wf_shade_blocks(int num_cus, int shade_waves);
-// true when the variant's camera trace skips Moller-Trumbore tests by the cull boxes
-bool wf_variant_culls(int variant);
-// true when the variant's secondary closest and shadow traces read leaf cull records (leafcull.hpp)
-bool wf_variant_leaf_cull(int variant);
-bool wf_variant_available(int variant); // compiled in (the default compile holds builds 0, 15, 18, 26)
-bool wf_perf_available(int variant);    // a performed-work instance of this trace build exists (18, 26)
 // cull boxes of this render's camera for the nrefs leaf references (+ 4 padding boxes)
 // and their unions per subtree (node_boxes[n_nodes]): leaves first, then the inner
 // nodes level by level from the deepest (levels: inner node ids grouped by depth,
 // level_off[i] = {offset, count} of level i, deepest first)
 int launch_cam_cull(const RenderArgs &A, uint32_t nrefs, float4 *boxes, float4 *node_boxes, const uint32_t *levels,
                     const uint32_t (*level_off)[2], int nlevels, hipStream_t st);
-void wf_trace_geometry(int variant, int num_cus, uint32_t &block, uint32_t &blocks);
-void wf_tail_geometry(int num_cus, uint32_t &block, uint32_t &blocks);
 // HIP events bracketing every trace launch (start, stop), recorded on the launch
 // stream; kind[i] = TK_* of pair i.  Grown by the launcher.
 struct TraceEvents {

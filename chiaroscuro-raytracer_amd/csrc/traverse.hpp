@@ -3,6 +3,7 @@
 #pragma once
 #include "leafcull.hpp"
 #include "render_common.hpp"
+#include "wfbuilds.hpp"
 
 namespace cr {
 
@@ -323,30 +324,7 @@ template <bool SC> __device__ __forceinline__ void load_fat(const DevScene &S, u
 // lane reads its box (16 B) and, inside, the record (48 B).
 // LC (secondary closest / shadow rays, unit directions; BF + SC): a leaf's tests run only
 // for the references its cull record (leafcull.hpp) cannot exclude for this ray and segment.
-// A trace build's configuration: every knob of trav_round and wf_trace (wavefront.hip), named.  The
-// defaults are the plain reference build; a build is a type deriving from this and restating what it
-// changes (wavefront.hip namespace tc), so a kernel reads e.g. wf_trace<cr::tc::ShadowLcFd>.
-struct TraceDefaults {
-    static constexpr bool SHADOW = false; // shadow (any-hit) queries, else closest-hit
-    static constexpr bool FULL = false;   // counting build: SURVEY §8d work counters and diagnostics
-    static constexpr int R = 8;           // LDS ring entries of the traversal stack per lane
-    static constexpr int MINW = 8;        // waves per SIMD the launch bounds ask for
-    static constexpr bool SC = false;     // scalar loads of wave-uniform nodes and leaves
-    static constexpr bool FD = false;     // exact short split division by the ray's RN(1/d)
-    static constexpr bool FAT = false;    // fat node records (a node and its children per load)
-    static constexpr bool CAM = false;    // the generation-1 closest (camera-ray) instantiation
-    static constexpr bool BF = false;     // branch-light steps and uniform-leaf tests by select
-    static constexpr int CULL = 0;        // camera cull boxes: 1 references and leaves, 2 also subtrees
-    static constexpr int LC = 0;          // leaf cull records (4 packed, 5 compressed)
-    static constexpr bool PC = false;     // performed-work counters (measurement only)
-    static constexpr bool DEAD = false;   // shadow queues with dead entries (wf_shade's chunked appends) skipped
-    static constexpr bool LX = false;     // a divergent leaf's masked tests spread over the wave (leaf_exchange)
-    static constexpr bool LXD = false;    // LX builds: the exchange's prefix by a DPP scan
-    // the options every real run leaves at their defaults fixed at compile time: WfArgs::vis_mark 1,
-    // WfArgs::ended_only 0 (no overlapped tail), RenderArgs::lc_debug 0 -- the launchers take such an
-    // instantiation only for a launch whose options have these values (wavefront.hip tc::Fixed)
-    static constexpr bool FIX = false;
-};
+// (a trace build's configuration type C -- TraceDefaults and the builds deriving from it: wfbuilds.hpp)
 
 // A lane's deferred leaf (LX builds): the references of the leaf whose first record is `first` that its
 // cull mask keeps (bit j: first + j).

@@ -1,6 +1,6 @@
 """Kernel-name classification shared by the profile summaries (rocprofv3 kernel names).
 
-The trace kernels are wf_trace<C> with C a build configuration of csrc/wavefront.hip's namespace
+The trace kernels are wf_trace<C> with C a build configuration of csrc/wfbuilds.hpp's namespace
 tc (cr::tc::ShadowFatLc5Fd, cr::tc::ClosestCount, cr::tc::ClosestFatLc5Perf, ...); the camera packet
 is wf_trace_packet<R, S, PC, FD>; the tail wf_tail<FULL, ...>.
 """

@@ -16,7 +16,7 @@ from helpers import Pair, assert_bitwise, rel_rmse
 pytestmark = pytest.mark.gpu
 
 ORACLE_KEYS = ("closest", "shadow", "inner", "leaf", "tritest", "hit", "texhit", "paths")
-# the wavefront trace builds (wavefront.hip kWf; the measured and superseded ones are removed, DESIGN.md
+# the wavefront trace builds (wfbuilds.hpp kWfBuilds; the measured and superseded ones are removed, DESIGN.md
 # keeps their numbers): the plain reference build 0, 15 (the packet camera
 # trace's fallback), round 2's default 18, 26 (leaf cull records), 40 / 42 (26 / 18 with the exact
 # short division in the camera packet), 43 / 44 (40 / 42 with it in the shadow trace) and the default 49

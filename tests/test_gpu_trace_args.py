@@ -1,7 +1,7 @@
 """The trace kernels' fixed options and point-of-use arguments, bit for bit against the oracle.
 
 The default builds (59 on the sponza stand-in, 44 on nanobox) launch trace instantiations with WfArgs::vis_mark 1,
-WfArgs::ended_only 0 and RenderArgs::lc_debug 0 fixed at compile time (wavefront.hip tc::Fixed); any other
+WfArgs::ended_only 0 and RenderArgs::lc_debug 0 fixed at compile time (wfbuilds.hpp tc::Fixed); any other
 value of such an option selects the build's generic kernels.  Every trace instantiation reads the queues,
 their counters and order and the result arrays from the kernel-argument segment once per query.  Each case
 below takes one of these paths; pixels and per-query counters must equal the oracle's in all of them.

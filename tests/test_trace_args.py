@@ -1,6 +1,6 @@
 """The trace kernels' registers and the kernel-argument offsets their device code assumes.
 
-The default builds' trace kernels (wavefront.hip tc::Fixed, builds 59 and 44) read what they need once per
+The default builds' trace kernels (wfbuilds.hpp tc::Fixed, builds 59 and 44) read what they need once per
 query -- the queues, their counters and order, the result arrays -- from the kernel-argument segment at the
 offsets KARG_W / KARG_G of csrc/kernels.hpp instead of holding it in scalar registers (or spill lanes of a
 VGPR) across the traversal.  A wrong offset would be a wild pointer, so the offsets are compared here with
