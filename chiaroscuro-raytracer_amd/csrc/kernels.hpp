@@ -287,6 +287,10 @@ struct WfArgs {
     // nee_zero; lean builds only -- the counting and performed-work builds trace every query) and
     // counted as a shadow query (option "wf_nee_skip")
     int nee_skip;
+    // 1: the camera packet decides a kd step at which every active ray takes the same single child once per
+    // packet, from the hull of its live rays' directions (wavefront.hip wf_trace_packet); 0: its setup marks
+    // every axis hull unusable, so every step is per lane (option "wf_packet_unanimous")
+    int packet_unanimous;
 };
 // The wavefront kernels take (RenderArgs A, WfArgs W, uint32_t g) by value, and the kernel-argument segment
 // holds the three one after another, each at its own alignment.  The trace kernels read the arguments they

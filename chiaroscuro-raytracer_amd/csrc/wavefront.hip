@@ -293,6 +293,11 @@ __device__ __forceinline__ WfArgs kargs_w(kargs_ptr p) {
     __builtin_memcpy(&w, p + KARG_W, sizeof(WfArgs));
     return w;
 }
+__device__ __forceinline__ RenderArgs kargs_a(kargs_ptr p) {
+    RenderArgs a;
+    __builtin_memcpy(&a, p + KARG_A, sizeof(RenderArgs));
+    return a;
+}
 __device__ __forceinline__ uint32_t kargs_g(kargs_ptr p) {
     return *(const __attribute__((address_space(4))) uint32_t *)(p + KARG_G);
 }
@@ -964,6 +969,22 @@ __global__ void __launch_bounds__(WF_TRACE_BLOCK, MINW) wf_tail(RenderArgs A, Wf
 // axis the near child could differ between lanes; the host then uses build 15's camera
 // trace for that render (RenderArgs::eye_on_split).
 enum : uint32_t { PACKET_DEPTH = 256 }; // >= the deepest tree cr_upload_scene accepts
+enum : uint32_t { EB_DEPTH = 24 };      // stack entries whose bounds the unanimous steps keep (below)
+// The maximum / minimum of v over the wave's 64 lanes, wave-uniform (no NaN among the inputs): a DPP scan
+// within the rows, the row totals broadcast onward, the result in lane 63.
+template <bool MAX> __device__ __forceinline__ float wave_minmax(float v) {
+    auto op = [](float a, int b) { return MAX ? fmaxf(a, __int_as_float(b)) : fminf(a, __int_as_float(b)); };
+    const auto bits = [](float x) { return __float_as_int(x); };
+    v = op(v, __builtin_amdgcn_update_dpp(bits(v), bits(v), 0x111, 0xf, 0xf, false)); // row_shr:1
+    v = op(v, __builtin_amdgcn_update_dpp(bits(v), bits(v), 0x112, 0xf, 0xf, false)); // row_shr:2
+    v = op(v, __builtin_amdgcn_update_dpp(bits(v), bits(v), 0x114, 0xf, 0xf, false)); // row_shr:4
+    v = op(v, __builtin_amdgcn_update_dpp(bits(v), bits(v), 0x118, 0xf, 0xf, false)); // row_shr:8
+    v = op(v, __builtin_amdgcn_update_dpp(bits(v), bits(v), 0x142, 0xa, 0xf, false)); // row_bcast:15
+    v = op(v, __builtin_amdgcn_update_dpp(bits(v), bits(v), 0x143, 0xc, 0xf, false)); // row_bcast:31
+    return __int_as_float(__builtin_amdgcn_readlane(bits(v), 63));
+}
+__device__ __forceinline__ float wave_max(float v) { return wave_minmax<true>(v); }
+__device__ __forceinline__ float wave_min(float v) { return wave_minmax<false>(v); }
 // S rays per lane (S = 2: a packet of 128 rays -- at 128 spp exactly one pixel's samples --
 // so the per-node scalar control work is shared by twice the rays).
 // The stack keeps per ray only the tmax at push (or INACTIVE): on pop a reactivated ray's
@@ -975,13 +996,48 @@ enum : uint32_t { PACKET_DEPTH = 256 }; // >= the deepest tree cr_upload_scene a
 // entry it owns.
 // FD: the split distance by the exact short division from the ray's RN(1/d) per axis, kept in
 // VGPRs (div_by_rcp: Markstein's correction, the full division outside its checked range).
+//
+// Unanimous steps (tests/native/packet_unanimous_check.cpp is the scheme on the CPU).  A step at
+// which EVERY active ray goes to the near child only, or every one to the far child only, changes no ray's
+// tmin, tmax or active flag and pushes nothing: it only sets the node.  Such a step is decided once per packet:
+// 1. Hull of the split distance.  Every lane's split distance is RN((split - oa) / d_a) bit for bit (FD:
+//    div_by_rcp_wave, scripts/markstein_check.c), the numerator is one number per node (one eye), and for a fixed
+//    numerator correctly rounded division is monotone in the divisor over divisors of one sign.  Per packet and
+//    axis, d_lo / d_hi are the min / max of d_a over the packet's LIVE rays, both rays of a lane (dead partial-tile
+//    slots and rays that missed the root box hold a placeholder direction and stay out).  tsp_lo / tsp_hi are the
+//    min / max of the same function at d_lo and d_hi, both in one short division (two lanes of a quad hold the
+//    ends, the next two their RN(1 / d)), so every lane's tsp lies in [tsp_lo, tsp_hi].  An axis hull is usable
+//    only if d_lo, d_hi have one sign, 2^-40 <= |d| <= 2^40 (the lanes' y is then RN(1 / d), not the NaN guard)
+//    and |d| of one end is at most twice the other's; a live ray with a NaN component or interval end, or
+//    WfArgs::packet_unanimous 0, makes all three unusable.  A step's quotients count only if both lie in
+//    2^-59 <= |q| <= 2^59: then 2^-60 <= |n * y| <= 2^60 held for both (n * y is within 2^-22 of the quotient
+//    unless it over- or underflows, and then the quotient lands outside; the factor 2 keeps one end's overflow
+//    from hiding behind the other's value in the min / max), so each is the short division's exact RN(n / d),
+//    non-zero, and both have one sign.  Anything else -- a NaN included -- takes the per-lane step.
+// 2. Bounds over the active rays: Tub >= max tmax, Mlb <= min tmin, wave-uniform (float bits in scalar registers;
+//    values >= +0 order like their bits, which is all the integer min below needs).  Active rays have
+//    tmin <= tmax: the root clip, both kinds of push and the parking rule keep it.
+// 3. The proofs.  Near-only for all: tsp_lo >= Tub or tsp_hi < 0.  Far-only for all: tsp_lo >= 0 and
+//    tsp_hi < Mlb -- strict, because a tie tsp == tmin == tmax is near-only in the reference; with both
+//    quotients non-zero and of one sign tsp_lo >= 0 is !(tsp_hi < 0).
+// 4. A proven step executes cn = nearc (or farc), the level bookkeeping and nothing else (the performed-work
+//    build counts a step per active ray as before).
+// 5. Keeping the bounds true.  Deactivating rays (cull boxes, hits) only shrinks the set.  A per-lane step on a
+//    usable axis: if no active ray stayed near-only, every ray that goes on crossed with tmax = its
+//    tsp <= tsp_hi, so Tub' = min(Tub, tsp_hi); Mlb' = Mlb.  The pushed entry's rays come back with
+//    tmax <= Tub(push) and tmin = their tsp >= tsp_lo(push) -- or, where far-only rays are parked in the entry
+//    with their own tmin, >= min(Mlb(push), tsp_lo(push)); an unusable axis pushes Mlb = -inf.  The two values
+//    are kept per stack entry in lanes 16 .. 63 of the hull's VGPR (v_writelane / v_readlane by sp); an entry at
+//    depth >= EB_DEPTH (a packet's stack holds one entry per step that split it, a few at a time) comes back
+//    with Tub = +inf, Mlb = -inf, which prove nothing until a later step or pop refreshes them.
+// The eye's three components ride in lanes 12 .. 14 of the same register (one v_readlane by the split axis).
 template <int R, int S, bool PC = false, bool FD = false>
 __global__ void __launch_bounds__(WF_TRACE_BLOCK, 8) wf_trace_packet(RenderArgs A, WfArgs W, uint32_t g) {
     extern __shared__ uint32_t pring_lds[]; // [R][blockDim][S] per-ray tmax bits at push
     __shared__ uint32_t pnode[4][PACKET_DEPTH];
     static_assert(S == 1 || S == 2, "one or two rays per lane");
     const DevScene &Sc = A.S;
-    const uint32_t tid = threadIdx.x, wv = tid >> 6, lane = tid & 63u, bdim = blockDim.x;
+    const uint32_t tid = threadIdx.x, wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6)), lane = tid & 63u, bdim = blockDim.x;
     const uint32_t gid = blockIdx.x * bdim + tid, gstride = W.gstride;
     uint32_t *ring = pring_lds;
     uint2 *gstk = W.gstack;
@@ -998,7 +1054,6 @@ __global__ void __launch_bounds__(WF_TRACE_BLOCK, 8) wf_trace_packet(RenderArgs 
     auto rfl = [](float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); };
     const float box_lo[3] = {rfl(Sc.bmin.x - eye.x), rfl(Sc.bmin.y - eye.y), rfl(Sc.bmin.z - eye.z)};
     const float box_hi[3] = {rfl(Sc.bmax.x - eye.x), rfl(Sc.bmax.y - eye.y), rfl(Sc.bmax.z - eye.z)};
-    const float eye_s[3] = {rfl(eye.x), rfl(eye.y), rfl(eye.z)};
     const uint32_t INACTIVE = 0xffffffffu;
     Ctr c = {};
     Pc pc = {};
@@ -1022,6 +1077,19 @@ __global__ void __launch_bounds__(WF_TRACE_BLOCK, 8) wf_trace_packet(RenderArgs 
         bool live[S], active[S], found[S];
         f3 d[S], y[S];
         float tmin[S], tmax[S], csx[S], csy[S];
+        // the unanimous steps' packet state (header comment): hq holds, in lanes 4a .. 4a + 3, axis a's hull of
+        // the live rays' components and its reciprocals (d_lo, d_hi, y(d_lo), y(d_hi); NaN: the axis always takes
+        // the per-lane step); Tub / Mlb are the two bounds over the active rays' intervals, as float bits in
+        // scalar registers; lanes 16 .. 63 of hq keep them per stack entry (sp < EB_DEPTH: Tub in lane 16 + sp,
+        // Mlb in lane 40 + sp; what the step computes in those lanes is never read)
+        float hq = __builtin_nanf("");
+        int32_t Tub, Mlb;
+        const int32_t P_INF = 0x7f800000, M_INF = (int32_t)0xff800000u;
+        { // the packet's setup reads its launch arguments where it uses them (kargs_here): none of them holds
+          // a scalar register, or a spill lane, across the node loop
+        const kargs_ptr ka = kargs_here();
+        const RenderArgs A = kargs_a(ka);
+        const WfArgs W = kargs_w(ka);
 #pragma unroll
         for (int s = 0; s < S; s++) {
             idx[s] = base + 64u * s + lane;
@@ -1089,6 +1157,45 @@ __global__ void __launch_bounds__(WF_TRACE_BLOCK, 8) wf_trace_packet(RenderArgs 
             }
             active[s] = live[s];
         }
+        {
+            float lo[3], hi[3], tub = -INFINITY, mlb = INFINITY;
+            bool odd = false; // a live ray with a NaN interval end or component: no bound holds for it
+#pragma unroll
+            for (int a = 0; a < 3; a++) lo[a] = INFINITY, hi[a] = -INFINITY;
+#pragma unroll
+            for (int s = 0; s < S; s++) {
+                const float dv[3] = {d[s].x, d[s].y, d[s].z};
+#pragma unroll
+                for (int a = 0; a < 3; a++) {
+                    lo[a] = live[s] ? fminf(lo[a], dv[a]) : lo[a];
+                    hi[a] = live[s] ? fmaxf(hi[a], dv[a]) : hi[a];
+                }
+                tub = live[s] ? fmaxf(tub, tmax[s]) : tub;
+                mlb = live[s] ? fminf(mlb, tmin[s]) : mlb;
+                odd = odd | (live[s] & ((tmax[s] != tmax[s]) | (tmin[s] != tmin[s]) | (dv[0] != dv[0]) |
+                                        (dv[1] != dv[1]) | (dv[2] != dv[2])));
+            }
+            const bool off = !W.packet_unanimous || __ballot(odd) != 0;
+            Tub = __builtin_amdgcn_readfirstlane(__float_as_int(wave_max(tub)));
+            Mlb = __builtin_amdgcn_readfirstlane(__float_as_int(wave_min(mlb)));
+            bool usable = false;
+            float e = 1.f;
+#pragma unroll
+            for (int a = 0; a < 3; a++) {
+                const float l = wave_min(lo[a]), h = wave_max(hi[a]);
+                const bool ok = !off && ((l > 0.f && h > 0.f) || (l < 0.f && h < 0.f)) && fabsf(l) >= 0x1p-40f &&
+                                fabsf(l) <= 0x1p40f && fabsf(h) >= 0x1p-40f && fabsf(h) <= 0x1p40f &&
+                                fmaxf(fabsf(l), fabsf(h)) <= 2.f * fminf(fabsf(l), fabsf(h));
+                const bool mine = (lane >> 2) == (uint32_t)a;
+                usable = mine ? ok : usable;
+                e = (mine & ok) ? ((lane & 1u) ? h : l) : e;
+            }
+            const float r = rcp_rn_wave(e); // == the lanes' y = RN(1 / d) inside the guard
+            hq = usable ? ((lane & 2u) ? r : e) : hq;
+            // (lanes 12 .. 14: the eye, read per step by the split axis)
+            hq = lane == 12u ? eye.x : (lane == 13u ? eye.y : (lane == 14u ? eye.z : hq));
+        }
+        }
         uint32_t cn = 0, sp = 0, nl = 0; // wave-uniform
         auto any_active = [&]() {
             bool a = false;
@@ -1101,7 +1208,12 @@ __global__ void __launch_bounds__(WF_TRACE_BLOCK, 8) wf_trace_packet(RenderArgs 
             return (csx[s] >= b.x) & (csx[s] <= b.y) & (csy[s] >= b.z) & (csy[s] <= b.w);
         };
         // push node with, per ray, its tmax (act) or INACTIVE
-        auto push = [&](uint32_t node, const bool (&act)[S]) {
+        auto push = [&](uint32_t node, const bool (&act)[S], int32_t eT, int32_t eM) {
+            if (sp < EB_DEPTH) { // the bounds its rays come back with: lanes 16 + sp and 40 + sp of hq
+                // (gfx9 allows v_writelane one scalar register: the lane comes from m0)
+                asm("v_writelane_b32 %0, %1, m0" : "+v"(hq) : "s"(eT), "{m0}"(16u + sp));
+                asm("v_writelane_b32 %0, %1, m0" : "+v"(hq) : "s"(eM), "{m0}"(16u + EB_DEPTH + sp));
+            }
             const uint32_t slot = (sp & (R - 1)) * bdim + tid;
             if (nl == (uint32_t)R) { // spill the oldest
                 if (PC) pc.vb += 8;
@@ -1141,7 +1253,14 @@ __global__ void __launch_bounds__(WF_TRACE_BLOCK, 8) wf_trace_packet(RenderArgs 
                     active[s] = act;
                     a = a | act;
                 }
-                if (__ballot(a)) return true;
+                if (__ballot(a)) { // the entry's bounds (deeper than the storage: none, until refreshed)
+                    const uint32_t el = sp < EB_DEPTH ? sp : 0u;
+                    const int32_t eT = __builtin_amdgcn_readlane(__float_as_int(hq), 16u + el);
+                    const int32_t eM = __builtin_amdgcn_readlane(__float_as_int(hq), 16u + EB_DEPTH + el);
+                    Tub = sp < EB_DEPTH ? eT : P_INF;
+                    Mlb = sp < EB_DEPTH ? eM : M_INF;
+                    return true;
+                }
             }
             return false;
         };
@@ -1219,59 +1338,102 @@ __global__ void __launch_bounds__(WF_TRACE_BLOCK, 8) wf_trace_packet(RenderArgs 
                 const float split = __uint_as_float(nd.x);
                 // the split axis is wave-uniform: the lanes' components are picked by scalar branches
                 // (one move per value, kept apart by the asm) instead of two v_cndmask per value
-                float oa, da[S], ya[S];
-                auto pick = [&](float e, const float (&dv)[S], const float (&yv)[S]) {
-                    oa = e;
+                if (PC) {
 #pragma unroll
-                    for (int s = 0; s < S; s++) {
-                        asm volatile("v_mov_b32 %0, %1" : "=v"(da[s]) : "v"(dv[s]));
-                        asm volatile("v_mov_b32 %0, %1" : "=v"(ya[s]) : "v"(yv[s]));
-                    }
-                };
-                if (a == 0) {
-                    float dv[S], yv[S];
-#pragma unroll
-                    for (int s = 0; s < S; s++) dv[s] = d[s].x, yv[s] = y[s].x;
-                    pick(eye_s[0], dv, yv);
-                } else if (a == 1) {
-                    float dv[S], yv[S];
-#pragma unroll
-                    for (int s = 0; s < S; s++) dv[s] = d[s].y, yv[s] = y[s].y;
-                    pick(eye_s[1], dv, yv);
-                } else {
-                    float dv[S], yv[S];
-#pragma unroll
-                    for (int s = 0; s < S; s++) dv[s] = d[s].z, yv[s] = y[s].z;
-                    pick(eye_s[2], dv, yv);
+                    for (int s = 0; s < S; s++) pc.steps += active[s] ? 1u : 0u;
                 }
-                const uint32_t below = oa < split ? 1u : 0u; // uniform: the eye is not on the plane
-                const uint32_t nearc = child + (1u - below), farc = child + below;
-                // (bitwise logic on the lane masks: no short-circuit branches)
-                float tsp[S];
-                bool crosses[S], after[S], to_near[S], to_far[S], anyn = false, anyf = false;
-#pragma unroll
-                for (int s = 0; s < S; s++) {
-                    if (PC) pc.steps += active[s] ? 1u : 0u;
-                    tsp[s] = FD ? div_by_rcp_wave(split - oa, da[s], ya[s]) : split_distance(split, oa, da[s]);
-                    crosses[s] = !(tsp[s] >= tmax[s]) & !(tsp[s] < 0.f); // !near_only
-                    after[s] = !(tsp[s] <= tmin[s]);                     // far_only = crosses & !after
-                    to_near[s] = active[s] & (!crosses[s] | after[s]);
-                    to_far[s] = active[s] & crosses[s];
-                    anyn = anyn | to_near[s];
-                    anyf = anyf | to_far[s];
-                }
-                if (!__ballot(anyn)) { // every active ray goes to the far child only
+                // the unanimous step: both hull ends' split distances in one short division (lanes 4a, 4a + 1),
+                // their min / max in both, the proofs as lane masks of which bit 4a counts.  A NaN hull or a
+                // quotient outside the short division's range clears `valid`; inside it both quotients are
+                // non-zero with one sign, so tsp_lo >= 0 is !(tsp_hi < 0)
+                const float oa = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(hq), 12u + a));
+                const float num = split - oa;
+                // (oa < split, uniform: the eye is not on the plane, and a difference of two floats is 0 only
+                // if they are equal)
+                const uint32_t nearc = child + ((uint32_t)__ballot(!(num > 0.f)) & 1u), farc = 2u * child + 1u - nearc;
+                const float hy = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(hq), 0xEE, 0xf, 0xf, false)); // quad_perm:[2,3,2,3]
+                const float hq0 = num * hy;
+                const float hqt = __builtin_fmaf(__builtin_fmaf(-hq0, hq, num), hy, hq0);
+                float al, ah; // the smaller and the larger magnitude of the two quotients
+                asm("s_nop 1\n\tv_min_f32_dpp %0, |%2|, |%2| quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+                    "v_max_f32_dpp %1, |%2|, |%2| quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf"
+                    : "=&v"(al), "=&v"(ah)
+                    : "v"(hqt));
+                const uint32_t bit = 1u << (4u * a);
+                const uint32_t hv = (uint32_t)__ballot(al >= 0x1p-59f) & (uint32_t)__ballot(ah <= 0x1p59f) & bit;
+                const uint32_t neg = (uint32_t)__ballot(hqt < 0.f), geT = (uint32_t)__ballot(al >= __int_as_float(Tub));
+                const uint32_t ltM = (uint32_t)__ballot(ah < __int_as_float(Mlb));
+                if ((neg | geT) & hv) { // every active ray goes to the near child only
+                    cn = nearc;
+                } else if (ltM & ~neg & hv) { // every active ray goes to the far child only
                     cn = farc;
                 } else {
-                    if (__ballot(anyf)) push(farc, to_far);
+                    // the split axis is wave-uniform: the lanes' components are picked by scalar branches
+                    // (one move per value, kept apart by the asm) instead of two v_cndmask per value
+                    float da[S], ya[S];
+                    auto pick = [&](const float (&dv)[S], const float (&yv)[S]) {
+#pragma unroll
+                        for (int s = 0; s < S; s++) {
+                            asm volatile("v_mov_b32 %0, %1" : "=v"(da[s]) : "v"(dv[s]));
+                            asm volatile("v_mov_b32 %0, %1" : "=v"(ya[s]) : "v"(yv[s]));
+                        }
+                    };
+                    if (a == 0) {
+                        float dv[S], yv[S];
+#pragma unroll
+                        for (int s = 0; s < S; s++) dv[s] = d[s].x, yv[s] = y[s].x;
+                        pick(dv, yv);
+                    } else if (a == 1) {
+                        float dv[S], yv[S];
+#pragma unroll
+                        for (int s = 0; s < S; s++) dv[s] = d[s].y, yv[s] = y[s].y;
+                        pick(dv, yv);
+                    } else {
+                        float dv[S], yv[S];
+#pragma unroll
+                        for (int s = 0; s < S; s++) dv[s] = d[s].z, yv[s] = y[s].z;
+                        pick(dv, yv);
+                    }
+                    // (bitwise logic on the lane masks: no short-circuit branches)
+                    float tsp[S];
+                    bool crosses[S], after[S], to_near[S], to_far[S], anyn = false, anyf = false, stay = false, parked = false;
 #pragma unroll
                     for (int s = 0; s < S; s++) {
-                        // both: near with tmax = tsplit; far only: parked with tmax = tmin
-                        const float nt = after[s] ? tsp[s] : tmin[s];
-                        tmax[s] = to_far[s] ? nt : tmax[s];
-                        active[s] = to_near[s];
+                        tsp[s] = FD ? div_by_rcp_wave(num, da[s], ya[s]) : num / da[s];
+                        crosses[s] = !(tsp[s] >= tmax[s]) & !(tsp[s] < 0.f); // !near_only
+                        after[s] = !(tsp[s] <= tmin[s]);                     // far_only = crosses & !after
+                        to_near[s] = active[s] & (!crosses[s] | after[s]);
+                        to_far[s] = active[s] & crosses[s];
+                        anyn = anyn | to_near[s];
+                        anyf = anyf | to_far[s];
+                        stay = stay | (active[s] & !crosses[s]);
+                        parked = parked | (to_far[s] & !after[s]);
                     }
-                    cn = nearc;
+                    if (!__ballot(anyn)) { // every active ray goes to the far child only
+                        cn = farc;
+                    } else {
+                        // the hull's ends here are > 0 (valid, and not below 0): as float bits they order like
+                        // integers against a bound of either sign
+                        if (__ballot(anyf)) {
+                            // the entry's rays come back with tmax <= Tub and tmin >= tsp_lo, or, if far-only rays
+                            // are parked in it with their own tmin, >= min(Mlb, tsp_lo)
+                            const int32_t hl = __builtin_amdgcn_readlane(__float_as_int(al), 4u * a);
+                            push(farc, to_far, Tub, hv ? ((__ballot(parked) && Mlb < hl) ? Mlb : hl) : M_INF);
+                        }
+#pragma unroll
+                        for (int s = 0; s < S; s++) {
+                            // both: near with tmax = tsplit; far only: parked with tmax = tmin
+                            const float nt = after[s] ? tsp[s] : tmin[s];
+                            tmax[s] = to_far[s] ? nt : tmax[s];
+                            active[s] = to_near[s];
+                        }
+                        // no near-only ray: every ray still active crossed, with tmax = its tsplit <= tsp_hi
+                        if (hv && !__ballot(stay)) {
+                            const int32_t hh = __builtin_amdgcn_readlane(__float_as_int(ah), 4u * a);
+                            Tub = hh < Tub ? hh : Tub;
+                        }
+                        cn = nearc;
+                    }
                 }
                 if (lvl == 1) { // cn's record is not in this fat record: fetch it
                     popit = false;

@@ -78,6 +78,9 @@ struct WfOptions {
     // sorted queues (round 5, sponza stand-in, two interleaved rounds: 256 -> 2270.9 / 2276.0, 512 -> 2313.8 /
     // 2314.6, 1024 -> 2318.1 / 2314.2 Mray/s -- the same-address append atomics, scripts/append_bench.hip)
     int wf_shade_block = 1024;
+    // WfArgs::packet_unanimous (option "wf_packet_unanimous"): the camera packet decides unanimous kd steps once
+    // per packet; 0: every step per lane -- the same image and counters
+    int wf_packet_unanimous = 1;
 };
 
 } // namespace cr

@@ -277,6 +277,7 @@ inline void wf_bind(const WfPlanIn &in, const WfPlan &pl, void *base, uint2 *gst
     W.vis_mark = o.wf_vis_mark && !o.wf_tail_overlap && in.K <= 63 ? 1 : 0;
     W.nee_skip = o.wf_nee_skip;
     W.tail_waves = o.wf_tail_waves;
+    W.packet_unanimous = o.wf_packet_unanimous;
 }
 
 } // namespace cr

@@ -390,7 +390,10 @@ int cr_get_trace_stats(cr_ctx *ctx, cr_trace_stats *out);
  *                   "refill_camera" (1..64 idle lanes of a wave that trigger a refill; 0: default)
  *   wavefront       "wf_paths", "wf_lanes", "wf_tail_min", "wf_tail_overlap", "wf_tail_waves", "wf_cam_lean",
  *                   "wf_cam_fuse", "wf_ctl_ray", "wf_vis_dw", "wf_vis_mark", "wf_nee_skip", "wf_shade_waves",
- *                   "wf_shade_block", "wf_app_chunk", "wf_resolve_paths", "wf_xcd", "wf_side_priority"
+ *                   "wf_shade_block", "wf_app_chunk", "wf_resolve_paths", "wf_xcd", "wf_side_priority",
+ *                   "wf_packet_unanimous" (1, the default: the camera packet decides a kd step at which every
+ *                   active ray takes the same single child once per packet; 0: every step per lane -- the same
+ *                   image and counters, for tests and same-library A/B runs)
  *   queue order     "wf_sort" (-1: by scene size), "wf_sort_min", "wf_sort_g1", "wf_sort_tile", "wf_dir_res",
  *                   "wf_dir_res_shadow", "wf_world_keys", "wf_world_bits", "wf_leaf_keys", "wf_leaf_shift"
  *   buffers, scene  "sample_buf_bytes", "sum_lds", "sum_staged", "node_bfs" (applies at the next upload),
