@@ -240,7 +240,7 @@ struct WfArgs {
     uint32_t measure_skip;
     uint32_t leaf_shift; // leaf keys: the node index >> leaf_shift (depth-first numbering: a run of
                          // consecutive nodes is one region of the tree)
-    // Overlapped tail (launch_wavefront_chunk): the tail kernel for closest queue g + 1 starts beside
+    // Overlapped tail (wfgen.hpp WfGenStep::overlap; launch_wavefront_chunk only): the tail kernel for closest queue g + 1 starts beside
     // the shadow trace of generation g.  tail_shadow_gen = g: wf_tail first traces each of its paths'
     // generation-g shadow ray and resolves that bounce itself; ended_only = 1: the shadow trace and
     // wf_resolve of generation g take only the paths that ended at g (bit 0 of the PS3 mark).
@@ -253,7 +253,7 @@ struct WfArgs {
     int key_bits_s;     // significant bits of the shadow queues' keys
     int tail_waves;     // waves per SIMD of the lean tail launch (4, 5, 6)
     int shade_waves;    // wf_shade's build: 8 waves per SIMD (64 VGPRs, spills) or else its natural 6
-    // wf_shade's queue appends in chunks (set per launch by launch_wavefront_chunk): a block reserves
+    // wf_shade's queue appends in chunks (set per launch: wfgen.hpp wf_app_chunk): a block reserves
     // app_chunk slots of a queue with one atomic and fills them over its iterations; the unused end of
     // its last chunk becomes dead entries (ray w = NO_PATH, key ~0) that the consumers skip.  0: one
     // atomic per block iteration.  Same-address device atomics serialise (~5.7 ns each on MI355X,
@@ -264,7 +264,7 @@ struct WfArgs {
     uint32_t shade_block; // wf_shade's threads per block for the per-iteration appends (256, 512, 1024)
     // 1: no wf_camera launch -- the packet camera trace derives each path's camera ray from its
     // (pixel, sample) itself, and wf_shade(1) / wf_resolve(1) take path p = ray p and the eye as
-    // its origin (set per chunk by launch_wavefront_chunk; option "wf_cam_fuse")
+    // its origin (set per chunk: wfgen.hpp wf_chunk_start; option "wf_cam_fuse")
     int cam_fused;
     // 1: a secondary closest ray carries its path's RNG counter in the direction's w and the key is
     // re-derived from the path's (pixel, sample) -- wf_shade neither reads nor writes the control slot
@@ -336,6 +336,8 @@ struct TraceEvents {
     int chunked = 0; // wf_shade launches that appended in chunks (WfArgs::app_chunk != 0)
 };
 // One chunk: camera, closest 1, then per generation shade, shadow || next closest, resolve.
+// Both drivers run wfgen.hpp's schedule through wavefront.hip's ChunkLauncher under their policy constant: the lanes
+// driver (WF_DRIVER_LANES) ignores sort_g1, never appends in chunks or overlaps the tail, and runs its lean tail at 4.
 // Two chunks in flight (cr_set_option "wf_lanes" 2): each lane owns a buffer set
 // (W, W.P = its capacity), a main and a side stream with fork / join events, an
 // event marking its queue lengths copied, and 2 pinned host words for them.  The

@@ -25,10 +25,13 @@
 // Queue appends are wave-aggregated (one atomic per wave, lane order kept), so
 // neighbouring paths -- samples of the same pixel -- stay neighbours in the
 // queues and the trace waves stay coherent.
+// Host side: a chunk's launches are scheduled once, by wfgen.hpp (pure, checked on the CPU), and executed once, by
+// ChunkLauncher; the two chunk drivers differ in how they wait for the queue lengths and in their WfDriver policy.
 #include "append.hpp"
 #include "camcull.hpp"
 #include "raysort.hpp"
 #include "traverse.hpp"
+#include "wfgen.hpp"
 
 #include <atomic>
 #include <thread>
@@ -145,16 +148,33 @@ __device__ __forceinline__ uint32_t sort_key(const RenderArgs &A, const WfArgs &
     return (lt * S * S + sub) * (W.dir_res * W.dir_res) + dir_bin(dir, W.dir_res);
 }
 
+// The key of a ray (o, d) that wf_shade(g) appends for path p from a hit record with w = hw (leaf + 1), dres direction
+// bins per axis: leaf keys, else pixel or world keys by wf_pixel_keys (wfgen.hpp: the host sorts at that kind's width)
+__device__ __forceinline__ uint32_t queue_key(const RenderArgs &A, const WfArgs &W, uint32_t g, uint32_t p, uint32_t hw,
+                                              f3 o, f3 d, uint32_t dres) {
+    return W.leaf_keys ? ((hw - 1u) >> W.leaf_shift) * (dres * dres) + dir_bin(d, dres)
+           : !wf_pixel_keys(W.leaf_keys, W.world_keys, g) ? world_key(A, W, o, d) : sort_key(A, W, p, d);
+}
+
 __device__ __forceinline__ void flush_tallies(const RenderArgs &A, unsigned long long *tl) {
     __syncthreads();
     if (threadIdx.x < T_N && tl[threadIdx.x]) atomicAdd(&A.counters[tally_slot(threadIdx.x)], tl[threadIdx.x]);
+}
+
+// Bounce k's records of path p in dw: {direct, shadow slot or answer} and {weight W_k, -}
+__device__ __forceinline__ float4 &dw_direct(const WfArgs &W, uint32_t k, uint32_t p) { return W.dw[(size_t)(2 * (k - 1)) * W.P + p]; }
+__device__ __forceinline__ float4 &dw_weight(const WfArgs &W, uint32_t k, uint32_t p) { return W.dw[(size_t)(2 * (k - 1) + 1) * W.P + p]; }
+// a dead queue entry j: no path (the consumers skip it), a placeholder direction
+__device__ __forceinline__ void dead_entry(float4 *q, size_t j) {
+    q[2 * j] = make_float4(0.f, 0.f, 0.f, __uint_as_float(NO_PATH));
+    q[2 * j + 1] = make_float4(0.f, 0.f, 1.f, 0.f);
 }
 
 // Back-to-front fold of a finished path (r_j = D_j + W_j * r_{j+1}) into samples[w].
 __device__ __forceinline__ void finish_path(const RenderArgs &A, const WfArgs &W, uint32_t p, uint32_t k, f3 tail) {
     f3 acc = tail;
     for (int j = (int)k - 2; j >= 0; j--) {
-        const float4 Dj = W.dw[(size_t)(2 * j) * W.P + p];
+        const float4 Dj = W.dw[(size_t)(2 * j) * W.P + p]; // (bounce j + 1's records, by the loop's signed index)
         const float4 Wj = W.dw[(size_t)(2 * j + 1) * W.P + p];
         acc = add(ld3(Dj), mul(ld3(Wj), acc));
     }
@@ -174,11 +194,6 @@ __device__ __forceinline__ void ctl_store(const WfArgs &W, uint32_t p, uint32_t 
     PS(W, PS_CTL, p) = make_float4(__uint_as_float(k), __uint_as_float(rng.key), __uint_as_float(rng.ctr), 0.f);
 }
 
-// Path state (PS above).  When generation 1 runs as wavefront launches (the chunk is not handed to
-// wf_tail at once), wf_camera writes only the resolve mark: wf_shade derives generation 1's
-// RNG state -- the camera sample's stream after its two jitter draws -- from the path's (pixel, sample)
-// instead of reading it.
-__host__ __device__ __forceinline__ bool camera_state_lean(const WfArgs &W) { return W.cam_lean && W.P >= W.tail_min; }
 // the key of path p's RNG stream: a function of its (pixel, sample) alone
 __device__ __forceinline__ uint32_t path_key(const RenderArgs &A, const WfArgs &W, uint32_t p) {
     const uint32_t w = W.w0 + p, item = w / A.s_count, s = A.s0 + (w - item * A.s_count);
@@ -219,8 +234,7 @@ __global__ void __launch_bounds__(256) wf_camera(RenderArgs A, WfArgs W) {
             W.ray[1][2 * (size_t)p + 1] = pk(d, 0u);
         } else if (p < W.P) {
             W.mark[p] = 0;
-            W.ray[1][2 * (size_t)p] = make_float4(0.f, 0.f, 0.f, __uint_as_float(NO_PATH));
-            W.ray[1][2 * (size_t)p + 1] = make_float4(0.f, 0.f, 1.f, 0.f);
+            dead_entry(W.ray[1], p);
         }
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) *cnt_closest(W, 1) = W.P;
@@ -240,7 +254,7 @@ __device__ __forceinline__ void shadow_store(const WfArgs &W, uint32_t g, uint32
     if (FIX || W.vis_mark) {
         if (!occluded) W.mark[idx & ~ENDED_BIT] = (uint8_t)((g << 2) | 2u | (idx >> 31));
     } else if (W.vis_dw) {
-        ((uint32_t *)(W.dw + (size_t)(2 * (g - 1)) * W.P + idx))[3] = occluded ? SHADOW_OCC : SHADOW_VIS;
+        ((uint32_t *)&dw_direct(W, g, idx))[3] = occluded ? SHADOW_OCC : SHADOW_VIS;
     } else {
         W.occ[idx] = occluded ? 1u : 0u;
     }
@@ -302,10 +316,22 @@ __device__ __forceinline__ uint32_t kargs_g(kargs_ptr p) {
     return *(const __attribute__((address_space(4))) uint32_t *)(p + KARG_G);
 }
 
+// A wave's queue fetch: the lanes of mask m take consecutive entries from `counter` with one atomic by the mask's
+// first lane.  Returns the first entry (wave-uniform); a lane's own is lane_rank(m) after it.
+__device__ __forceinline__ uint32_t wave_take(uint32_t *counter, uint64_t m, uint32_t lane) {
+    const uint32_t leader = (uint32_t)__ffsll((long long)m) - 1u;
+    uint32_t base = 0;
+    if (lane == leader) base = atomicAdd(counter, (uint32_t)__popcll(m));
+    return __shfl(base, (int)leader, 64);
+}
+__device__ __forceinline__ uint32_t lane_rank(uint64_t m) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+
 template <class C>
 __global__ void __launch_bounds__(WF_TRACE_BLOCK, C::MINW) wf_trace(RenderArgs A, WfArgs W, uint32_t g) {
     static constexpr bool SHADOW = C::SHADOW, FULL = C::FULL, CAM = C::CAM, PC = C::PC, FIX = C::FIX;
-    static constexpr int CULL = C::CULL;
+    static constexpr int CULL = C::CULL, KIND = SHADOW ? TK_SHADOW : (CAM ? TK_CAMERA : TK_CLOSEST);
     static_assert(!CULL || (CAM && !SHADOW), "the cull applies to camera rays");
     extern __shared__ uint2 ring_lds[];
     const DevScene &S = A.S;
@@ -314,7 +340,7 @@ __global__ void __launch_bounds__(WF_TRACE_BLOCK, C::MINW) wf_trace(RenderArgs A
     const uint32_t n = SHADOW ? *cnt_shadow(W, g) : *cnt_closest(W, g);
     Ctr c = {};
     Diag dg = {};
-    dg.on = FULL && ((A.diag_kinds >> (SHADOW ? TK_SHADOW : (CAM ? TK_CAMERA : TK_CLOSEST))) & 1u);
+    dg.on = FULL && ((A.diag_kinds >> KIND) & 1u);
     uint32_t state = ST_NEED_WORK, idx = 0, exclude = 0;
     uint32_t issued = 0; // the wave's queries (wave-uniform: an SGPR, not a VGPR per lane)
     f3 o = mk(0.f, 0.f, 0.f), d = mk(0.f, 0.f, 1.f);
@@ -348,19 +374,14 @@ __global__ void __launch_bounds__(WF_TRACE_BLOCK, C::MINW) wf_trace(RenderArgs A
                     if (state == ST_NEED_WORK) state = ST_DONE;
                     break;
                 }
-                const uint32_t leader = (uint32_t)__ffsll((long long)m) - 1u;
                 bool iss = false;
                 const uint32_t lo = xp ? (uint32_t)((uint64_t)n * part / WF_XCDS) : 0u;
                 const uint32_t hi = xp ? (uint32_t)((uint64_t)n * (part + 1) / WF_XCDS) : n;
-                uint32_t base = 0;
-                if (lane == leader)
-                    base = atomicAdd(xp ? xwork + part * WF_XSTRIDE : work, (uint32_t)__popcll(m));
-                base = lo + __shfl(base, (int)leader, 64);
+                const uint32_t base = lo + wave_take(xp ? xwork + part * WF_XSTRIDE : work, m, lane);
                 if (xp && base + (uint32_t)__popcll(m) > hi) // this range is drained: the next one
                     xs = (xs & ~255u) + 256u + (part + 1) % WF_XCDS;
                 if (state == ST_NEED_WORK) {
-                    idx = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
-                                                           __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+                    idx = base + lane_rank(m);
                     if (idx >= hi) {
                         if (!xp) state = ST_DONE; // else: stays idle and takes a ray of the next range
                     } else {
@@ -468,10 +489,10 @@ __global__ void __launch_bounds__(WF_TRACE_BLOCK, C::MINW) wf_trace(RenderArgs A
     flush_counters(A.counters, c, SHADOW ? 2u : 1u); // (the count is the wave's already)
     if (PC) {
         pc.q = lane == 0 ? issued : 0u;
-        pc_flush(A.counters + CTR_PERF + PERF_N * (SHADOW ? TK_SHADOW : (CAM ? TK_CAMERA : TK_CLOSEST)), pc);
+        pc_flush(A.counters + CTR_PERF + PERF_N * KIND, pc);
     }
     if (FULL) { // per-instantiation split of the §8d work counters (bench roofline)
-        unsigned long long *base = A.counters + CTR_TRACE + 3 * (SHADOW ? TK_SHADOW : (CAM ? TK_CAMERA : TK_CLOSEST));
+        unsigned long long *base = A.counters + CTR_TRACE + 3 * KIND;
         const uint32_t v[3] = {c.inner, c.leaf, c.tritest};
 #pragma unroll
         for (int i = 0; i < 3; i++) {
@@ -488,15 +509,39 @@ __global__ void __launch_bounds__(WF_TRACE_BLOCK, C::MINW) wf_trace(RenderArgs A
 // Shared by the per-generation kernels (wf_shade / wf_bounce) and the tail
 // kernel (wf_tail), so both execute the same arithmetic on the same state.
 
-// RayTracer::sendRay up to the shadow query (rayTracer.cpp:80-99) for a closest
-// hit of path p: hit shading, emission, NEE light sample.  Writes the path state
-// (slot 3's w -- the shadow-queue slot -- is left to the caller).  Returns the
-// shadow ray in `sh` when the scene has lights.
 struct ShadowRay {
     f3 o, d;
     float dist;
     uint32_t light;
 };
+// The NEE light sample at a hit, when the scene has lights: the contribution, the next ray's origin and the shadow
+// ray.  skipped: the query is answered without a trace (nee_zero; counted either way); true: the ray is traced
+__device__ __forceinline__ bool nee_sample(const RenderArgs &A, const WfArgs &W, const HitShade &hs, Rng &rng, f3 &contrib,
+                                           f3 &next, ShadowRay &sh, bool &skipped) {
+    if (!A.S.nlights) return false;
+    const Nee e = sample_light(A.S, hs.p, hs.normal, hs.fcol, rng);
+    contrib = e.contrib;
+    next = e.origin;
+    sh = ShadowRay{e.origin, e.dir, e.distance, e.light};
+    skipped = nee_zero(W, A, contrib, hs.direct);
+    return !skipped;
+}
+// The BRDF sample and Russian roulette in the reference's draw order; true: the path continues along wi at weight w
+__device__ __forceinline__ bool brdf_step(f3 normal, f3 fcol, Rng &rng, f3 &wi, f3 &w) {
+    const float sx = rng_uniform(rng, -1.f, 1.f);
+    const float sy = rng_uniform(rng, -1.f, 1.f);
+    float pdf;
+    sample_wi(normal, sx, sy, wi, pdf);
+    const float Kmax = std_max(std_max(fcol.x, fcol.y), fcol.z);
+    if (pdf == 0.f || rng_uniform(rng, 0.f, 1.f) > Kmax) return false;
+    const float cosine = fabsf(dot(normal, wi));
+    w = divs(muls(fcol, cosine), pdf * Kmax);
+    return true;
+}
+// RayTracer::sendRay up to the shadow query (rayTracer.cpp:80-99) for a closest
+// hit of path p: hit shading, emission, NEE light sample.  Writes the path state
+// (slot 3's w -- the shadow-queue slot -- is left to the caller).  Returns the
+// shadow ray in `sh` when the scene has lights.
 __device__ __forceinline__ bool shade_path(const RenderArgs &A, const WfArgs &W, uint32_t p, f3 ro, uint4 h,
                                            bool &textured, ShadowRay &sh) {
     const DevScene &S = A.S;
@@ -506,17 +551,8 @@ __device__ __forceinline__ bool shade_path(const RenderArgs &A, const WfArgs &W,
     textured = hs.textured;
     Rng rng{__float_as_uint(ctl.y), __float_as_uint(ctl.z)};
     f3 contrib = mk(0.f, 0.f, 0.f), next = add(hs.p, muls(hs.normal, 0.001f));
-    bool nee = false;
-    if (S.nlights) {
-        const Nee e = sample_light(S, hs.p, hs.normal, hs.fcol, rng);
-        contrib = e.contrib;
-        next = e.origin;
-        sh.o = e.origin;
-        sh.d = e.dir;
-        sh.dist = e.distance;
-        sh.light = e.light;
-        nee = !nee_zero(W, A, contrib, hs.direct); // (the caller counts the query either way)
-    }
+    bool skipped = false;
+    const bool nee = nee_sample(A, W, hs, rng, contrib, next, sh, skipped);
     PS(W, 0, p) = pk(hs.direct, 0u);
     PS(W, 1, p) = pk(hs.fcol, 0u);
     PS(W, 2, p) = pk(hs.normal, 0u);
@@ -542,19 +578,13 @@ __device__ __forceinline__ bool bounce_path(const RenderArgs &A, const WfArgs &W
         finish_path(A, W, p, k, direct);
         return false;
     }
-    const float sx = rng_uniform(rng, -1.f, 1.f);
-    const float sy = rng_uniform(rng, -1.f, 1.f);
-    float pdf;
-    sample_wi(normal, sx, sy, wi, pdf);
-    const float Kmax = std_max(std_max(fcol.x, fcol.y), fcol.z);
-    if (pdf == 0.f || rng_uniform(rng, 0.f, 1.f) > Kmax) {
+    f3 w;
+    if (!brdf_step(normal, fcol, rng, wi, w)) {
         finish_path(A, W, p, k, direct);
         return false;
     }
-    const float cosine = fabsf(dot(normal, wi));
-    const f3 w = divs(muls(fcol, cosine), pdf * Kmax);
-    W.dw[(size_t)(2 * (k - 1)) * W.P + p] = pk(direct, 0u);
-    W.dw[(size_t)(2 * (k - 1) + 1) * W.P + p] = pk(w, 0u);
+    dw_direct(W, k, p) = pk(direct, 0u);
+    dw_weight(W, k, p) = pk(w, 0u);
     ctl_store(W, p, k + 1, rng);
     org = ld3(PS(W, 4, p));
     return true;
@@ -587,30 +617,12 @@ __device__ __forceinline__ bool shade_next(const RenderArgs &A, const WfArgs &W,
         rng = Rng{__float_as_uint(ctl.y), __float_as_uint(ctl.z)};
     }
     f3 contrib = mk(0.f, 0.f, 0.f), next = add(hs.p, muls(hs.normal, 0.001f));
-    bool nee = false;
-    if (S.nlights) {
-        const Nee e = sample_light(S, hs.p, hs.normal, hs.fcol, rng);
-        contrib = e.contrib;
-        next = e.origin;
-        sh.o = e.origin;
-        sh.d = e.dir;
-        sh.dist = e.distance;
-        sh.light = e.light;
-        nee = true;
-        skipped = nee_zero(W, A, contrib, hs.direct);
-        nee = !skipped;
-    }
+    const bool nee = nee_sample(A, W, hs, rng, contrib, next, sh, skipped);
     cont = false;
     if ((int)k != A.K) {
-        const float sx = rng_uniform(rng, -1.f, 1.f);
-        const float sy = rng_uniform(rng, -1.f, 1.f);
-        float pdf;
-        sample_wi(hs.normal, sx, sy, wi, pdf);
-        const float Kmax = std_max(std_max(hs.fcol.x, hs.fcol.y), hs.fcol.z);
-        if (!(pdf == 0.f || rng_uniform(rng, 0.f, 1.f) > Kmax)) {
-            const float cosine = fabsf(dot(hs.normal, wi));
-            const f3 w = divs(muls(hs.fcol, cosine), pdf * Kmax);
-            W.dw[(size_t)(2 * (k - 1) + 1) * W.P + p] = pk(w, 0u);
+        f3 w;
+        if (brdf_step(hs.normal, hs.fcol, rng, wi, w)) {
+            dw_weight(W, k, p) = pk(w, 0u);
             if (W.ctl_ray) ctr = rng.ctr;
             else ctl_store(W, p, k + 1, rng);
             org = next;
@@ -689,25 +701,17 @@ __global__ void __launch_bounds__(BS, MINW) wf_shade(RenderArgs A, WfArgs W, uin
         if (CH) block_append_chunk<2>(queues, want, app2, it & 1u, C, cb, cu, slots);
         else block_append_n<2>(queues, want, app2, it & 1u, slots);
         const uint32_t j = slots[0], jc = slots[1];
-        if (hit) W.dw[(size_t)(2 * (g - 1)) * W.P + p] = pk(direct, nee ? j : NO_SLOT);
+        if (hit) dw_direct(W, g, p) = pk(direct, nee ? j : NO_SLOT);
         if (nee) {
             W.sray[2 * (size_t)j] = pk(sh.o, p);
             W.sray[2 * (size_t)j + 1] = make_float4(sh.d.x, sh.d.y, sh.d.z, sh.dist);
             W.sexcl[j] = sh.light | (cont ? SEXCL_CONT : 0u);
-            if (W.sort) {
-                W.key[0][0][j] = W.leaf_keys ? ((h.w - 1u) >> W.leaf_shift) * (W.dir_res_s * W.dir_res_s) + dir_bin(sh.d, W.dir_res_s)
-                                 : (W.world_keys && g >= (uint32_t)W.world_keys) ? world_key(A, W, sh.o, sh.d)
-                                                                                 : sort_key(A, W, p, sh.d);
-            }
+            if (W.sort) W.key[0][0][j] = queue_key(A, W, g, p, h.w, sh.o, sh.d, W.dir_res_s);
         }
         if (cont) {
             next_rays[2 * (size_t)jc] = pk(org, p);
             next_rays[2 * (size_t)jc + 1] = pk(wi, W.ctl_ray ? ctr : 0u);
-            if (W.sort) {
-                W.key[1][0][jc] = W.leaf_keys ? ((h.w - 1u) >> W.leaf_shift) * (W.dir_res * W.dir_res) + dir_bin(wi, W.dir_res)
-                                  : (W.world_keys && g >= (uint32_t)W.world_keys) ? world_key(A, W, org, wi)
-                                                                                  : sort_key(A, W, p, wi);
-            }
+            if (W.sort) W.key[1][0][jc] = queue_key(A, W, g, p, h.w, org, wi, W.dir_res);
         }
         tally(tl, T_HIT, hit);
         tally(tl, T_TEXHIT, textured);
@@ -726,8 +730,7 @@ __global__ void __launch_bounds__(BS, MINW) wf_shade(RenderArgs A, WfArgs W, uin
             float4 *rq = q ? next_rays : W.sray;
             for (uint32_t k = threadIdx.x; k < len; k += blockDim.x) {
                 const uint32_t j = from + k;
-                rq[2 * (size_t)j] = make_float4(0.f, 0.f, 0.f, __uint_as_float(NO_PATH));
-                rq[2 * (size_t)j + 1] = make_float4(0.f, 0.f, 1.f, 0.f);
+                dead_entry(rq, j);
                 if (!q) W.sexcl[j] = 0u;
                 if (W.sort) {
                     W.key[q][0][j] = 0xffffffffu;
@@ -840,13 +843,9 @@ __global__ void __launch_bounds__(WF_TRACE_BLOCK, MINW) wf_tail(RenderArgs A, Wf
         const uint64_t need_m = __ballot(state == ST_NEED_WORK);
         const uint64_t busy_m = __ballot(state == ST_CLOSEST || state == ST_SHADOW);
         if (need_m && (busy_m == 0 || (uint32_t)__popcll(need_m) >= A.refill)) {
-            const uint32_t leader = (uint32_t)__ffsll((long long)need_m) - 1u;
-            uint32_t base = 0;
-            if (lane == leader) base = atomicAdd(work, (uint32_t)__popcll(need_m));
-            base = __shfl(base, (int)leader, 64);
+            const uint32_t base = wave_take(work, need_m, lane);
             if (state == ST_NEED_WORK) {
-                const uint32_t idx = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(need_m >> 32),
-                                                                     __builtin_amdgcn_mbcnt_lo((uint32_t)need_m, 0u));
+                const uint32_t idx = base + lane_rank(need_m);
                 if (idx >= n) {
                     state = ST_DONE;
                 } else {
@@ -859,7 +858,7 @@ __global__ void __launch_bounds__(WF_TRACE_BLOCK, MINW) wf_tail(RenderArgs A, Wf
                     if (W.ctl_ray && g0 >= 2 && p != NO_PATH)
                         ctl_store(W, p, g0, Rng{path_key(A, W, p), __float_as_uint(r1.w)});
                     const uint32_t slot = (gs && p != NO_PATH)
-                                              ? __float_as_uint(W.dw[(size_t)(2 * (gs - 1)) * W.P + p].w) : NO_SLOT;
+                                              ? __float_as_uint(dw_direct(W, gs, p).w) : NO_SLOT;
                     if (slot != NO_SLOT) { // overlapped: this path's generation-gs shadow query first
                         const float4 s0 = W.sray[2 * (size_t)slot], s1 = W.sray[2 * (size_t)slot + 1];
                         if (PC) pc.vb += 36;
@@ -879,7 +878,7 @@ __global__ void __launch_bounds__(WF_TRACE_BLOCK, MINW) wf_tail(RenderArgs A, Wf
         // advance every lane whose query has a result, until it has a new query or is idle
         while (state >= ST_HIT) {
             if (pend) { // overlapped: resolve bounce gs (wf_resolve's resolve_path, a path that continues)
-                float4 &dk = W.dw[(size_t)(2 * (gs - 1)) * W.P + p];
+                float4 &dk = dw_direct(W, gs, p);
                 f3 direct = ld3(dk);
                 if (state == ST_VISIBLE) direct = add(direct, ld3(PS(W, 3, p)));
                 dk = pk(direct, 0u);
@@ -1491,13 +1490,6 @@ static int launch_wf(WfKernel k, uint32_t blocks, size_t lds, hipStream_t s, con
 static bool fixed_options(const RenderArgs &A, const WfArgs &W) {
     return wf_fixed_options(W.vis_mark, W.ended_only, A.lc_debug);
 }
-// The chunk's camera rays come from the packet trace itself (WfArgs::cam_fused) when the ctx asks for it
-// (W.cam_fused on entry), the camera kernel is the packet trace, generation 1 runs as its own launches
-// (not handed to wf_tail, which reads wf_camera's rays) and wf_shade derives generation 1's RNG state.
-static bool camera_fuses(const WfBuild &b, const RenderArgs &A, const WfArgs &W) {
-    return W.cam_fused && b.packet && !A.eye_on_split && camera_state_lean(W);
-}
-
 // One thread per leaf reference: its cull box for this render's camera (camcull.hpp),
 // from the record's A, e1, e2 -- the floats the triangle test uses.  Boxes
 // nrefs..nrefs+3 are empty (the four-box scalar loads of uniform leaves read past a
@@ -1577,23 +1569,15 @@ int launch_query_trace(const RenderArgs &A, const WfArgs &W, uint32_t g, bool sh
     return (int)hipGetLastError();
 }
 
-// Sorts the queue of n rays whose keys wf_shade wrote into key / perm set `set`
-// (0 shadow, 1 closest); returns the permutation for the trace kernel (nullptr:
-// trace in queue order).
-// pixel: the queue's keys are pixel keys (wf_shade of a generation below world_keys), which
-// need fewer bits than world keys -- one digit pass fewer for a rank's share of a frame
-static const uint32_t *order_queue(const WfArgs &W, int set, uint32_t n, hipStream_t st, int &err, bool pixel) {
-    if (!W.sort || err || n < W.sort_min || (W.measure_skip & 2u)) return nullptr;
+// Sorts the queue of n rays whose keys wf_shade wrote into key / perm set `set` (0 shadow, 1 closest) at `bits` key
+// bits (whether and how wide: wfgen.hpp wf_gen_step); returns the permutation for the trace kernel.
+static const uint32_t *order_queue(const WfArgs &W, int set, uint32_t n, int bits, hipStream_t st, int &err) {
     uint32_t *keys[2] = {W.key[set][0], W.key[set][1]}, *vals[2] = {W.perm[set][0], W.perm[set][1]};
     size_t tb = W.sort_tmp_bytes;
-    const int bits = pixel ? W.key_bits_pixel : (set == 0 ? W.key_bits_s : W.key_bits);
     // (the trace reads the permutation only: the last pass writes no keys)
     const int sel = sort_queue(keys, vals, n, bits, W.sort_tmp, tb, st, false, true, false);
-    if (sel < 0) {
-        err = (int)hipErrorUnknown;
-        return nullptr;
-    }
-    return vals[sel];
+    if (sel < 0) err = (int)hipErrorUnknown;
+    return sel < 0 ? nullptr : vals[sel];
 }
 
 // Records a (start, stop) event pair around one trace launch when te is given.
@@ -1649,58 +1633,42 @@ uint32_t wf_shade_blocks(int num_cus, int shade_waves) {
     return std::max(shade_grid(num_cus, wf_shade_kernel(256u, 256u, shade_waves)),
                     shade_grid(num_cus, wf_shade_kernel(1024u, 1024u, 8)));
 }
-// wf_shade at the ctx's option "wf_shade_waves" (8, the default since round 4; or 6)
-// The append chunk of a wf_shade launch over nin rays (WfArgs::app_chunk): a power of two giving each
-// block about 16 chunks per queue, so the dead entries stay a few percent of the queue; 0 (one atomic
-// per block iteration) for queues that short, and at most what the queues' spare slots hold for every
-// block's partial last chunk.  Only for queues traced in append order (W.sort 0: scenes below
-// SORT_MIN_TRIS): round 5, two interleaved rounds, cornell_box 13,002 / 13,000 -> 14,331 / 14,298 Mray/s;
-// on sorted queues (sponza stand-in) wf_shade gains 9 % but the shadow trace loses 1.7 % -- the chunks
-// change the order among equal keys -- 2278.5 / 2278.7 -> 2274.8 / 2270.4
-static uint32_t shade_app_chunk(const WfArgs &W, uint32_t nin, int num_cus) {
-    if (!W.qspare) return 0u;
-    const uint32_t grid = wf_shade_blocks(num_cus, W.shade_waves);
-    const uint32_t want = nin / (grid * 16u), cap = W.qspare / grid;
-    if (W.app_force) return W.app_force <= cap ? W.app_force : 0u;
-    if (W.sort) return 0u;
-    uint32_t c = 256u;
-    while (c * 2u <= want && c * 2u <= cap && c < 4096u) c *= 2u;
-    return c <= want && c <= cap ? c : 0u;
-}
-static void launch_shade(const RenderArgs &A, const WfArgs &W, uint32_t g, int num_cus, hipStream_t st) {
-    const int id = wf_shade_kernel(W.app_chunk, W.shade_block, W.shade_waves); // (exists for every input)
-    hipLaunchKernelGGL(shade_kernel(ShadeKernels{}, id), dim3(shade_grid(num_cus, id)), dim3(shade_desc(id).bs), 0, st,
-                       A, W, g);
-}
-
-// The host side of a chunk's launches, shared by the two chunk drivers below (launch_wavefront_chunk: one
-// chunk, generation by generation; run_wavefront_lanes: two chunks in flight): the render's trace build, the
-// grids, and the launches with their trace events.  A launch that fails leaves its error in err and the
-// launches after it do nothing more than return; the drivers test err after each.
+// The host side of a chunk, shared by the two chunk drivers below: the render's trace build, the grids, the launches
+// with their trace events, and the one executor of what wfgen.hpp schedules -- start(), shade(), trace() -- under the
+// driver's policy `drv`.  A failed launch leaves its error in err and the launches after it only return.
+struct ChunkRun { // a chunk in flight
+    WfArgs W;
+    hipStream_t st, side;    // its main and side stream, the fork / join events between them
+    hipEvent_t fork, join;
+    uint32_t *cnt;           // host words for the lengths of shadow queue g and closest queue g + 1
+    uint32_t g = 1, nin = 0; // the generation wf_shade runs next; the rays of its closest queue
+    bool dead = false;       // shadow queue g may hold dead entries (wf_shade appended in chunks)
+};
 struct ChunkLauncher {
     const RenderArgs &A;
     const int num_cus;
     TraceEvents *const te;
+    const WfDriver drv;
     const WfMode mode;
     const WfBuild *const b; // (null: no such build in this mode -- check() refuses the chunk)
     uint32_t blocks = 0;
     size_t lds = 0;
     uint32_t sgrid; // grid-stride phases
     int err = 0;
-    ChunkLauncher(const RenderArgs &A_, int num_cus_, TraceEvents *te_)
-        : A(A_), num_cus(num_cus_), te(te_), mode(wf_mode(A_.full_counters, A_.perf_counters)),
+    ChunkLauncher(const RenderArgs &A_, int num_cus_, TraceEvents *te_, const WfDriver &drv_)
+        : A(A_), num_cus(num_cus_), te(te_), drv(drv_), mode(wf_mode(A_.full_counters, A_.perf_counters)),
           b(wf_render_build(A_.variant, mode)) {
         if (b) blocks = wf_trace_blocks(b->id, num_cus), lds = wf_ring_bytes(b->ring);
         sgrid = (uint32_t)(num_cus > 0 ? num_cus : 256) * 8;
     }
+    // the tail kernel this driver launches for a chunk bound as W
+    int tail_id(const WfArgs &W) const { return wf_tail_kernel(*b, mode, wf_tail_waves(drv, W.tail_waves)); }
     // A chunk whose stack-overflow areas were sized for a grid of gstride threads can run: the stride covers the
-    // trace grid and the tail grid this driver launches (lean_waves as passed to tail()).  The verdict is the
-    // trace grid's alone for every build there is: each runs 8 trace blocks per CU (wfbuilds.hpp `waves`) and no
-    // tail more than 6, so a stride that covers the first covers the second.
-    int check(uint32_t gstride, int lean_waves) const {
-        if (!b) return (int)hipErrorInvalidValue;
-        const int t = wf_tail_kernel(*b, mode, lean_waves);
-        if (t < 0 || gstride < WF_TRACE_BLOCK * blocks || gstride < WF_TRACE_BLOCK * wf_tail_blocks(t, num_cus))
+    // trace grid and this driver's tail grid.  The verdict is the trace grid's alone for every build there is: each
+    // runs 8 trace blocks per CU (wfbuilds.hpp `waves`) and no tail more than 6.
+    int check(const WfArgs &W) const {
+        const int t = b ? tail_id(W) : -1;
+        if (t < 0 || W.gstride < WF_TRACE_BLOCK * blocks || W.gstride < WF_TRACE_BLOCK * wf_tail_blocks(t, num_cus))
             return (int)hipErrorInvalidValue;
         return 0;
     }
@@ -1708,9 +1676,9 @@ struct ChunkLauncher {
         if ((err = trace_event(te, s, kind, true)) || (err = launch_wf(k, grid, bytes, s, A, W, g))) return;
         err = trace_event(te, s, kind, false);
     }
-    // the rest of the chunk from closest queue g on, in one launch; the lean build at lean_waves per SIMD
-    void tail(uint32_t g, hipStream_t s, WfArgs Wt, int lean_waves) {
-        const int t = wf_tail_kernel(*b, mode, lean_waves);
+    // the rest of the chunk from closest queue g on, in one launch
+    void tail(uint32_t g, hipStream_t s, WfArgs Wt) {
+        const int t = tail_id(Wt);
         Wt.order = nullptr;
         launch(TK_TAIL, tail_kernel(TailKernels{}, t), t < 0 ? 0u : wf_tail_blocks(t, num_cus),
                t < 0 ? 0 : wf_ring_bytes(tail_desc(t).ring), s, Wt, g);
@@ -1726,160 +1694,90 @@ struct ChunkLauncher {
         launch(g == 1 ? TK_CAMERA : TK_CLOSEST, k, blocks, lds, s, Wc, g);
     }
     // shadow trace of generation g (Ws: with the queue's order; dead: the queue may hold dead entries), then
-    // wf_resolve of that generation with Wr
-    void shadow_resolve(const WfArgs &Ws, const WfArgs &Wr, uint32_t g, hipStream_t s, bool dead) {
+    // wf_resolve of that generation
+    void shadow_resolve(const WfArgs &Ws, uint32_t g, hipStream_t s, bool dead) {
         launch(TK_SHADOW, trace_kernel(TraceKernels{}, wf_shadow_kernel(*b, mode, fixed_options(A, Ws), dead)), blocks, lds,
                s, Ws, g);
-        if (err) return;
-        if (!(Wr.measure_skip & 1u)) hipLaunchKernelGGL(wf_resolve, dim3(sgrid), dim3(256), 0, s, A, Wr, g);
+        if (!err && !(Ws.measure_skip & 1u)) hipLaunchKernelGGL(wf_resolve, dim3(sgrid), dim3(256), 0, s, A, Ws, g);
+    }
+    // The chunk's start (wf_chunk_start): wf_camera unless the camera is fused, then the camera trace -- or the
+    // whole chunk in wf_tail(1).  true: wf_shade(1) is next
+    bool start(ChunkRun &r) {
+        WfArgs &W = r.W;
+        const WfStart s = wf_chunk_start(W, b->packet, A.eye_on_split != 0);
+        W.cam_fused = s.cam_fused ? 1 : 0;
+        if (s.camera) hipLaunchKernelGGL(wf_camera, dim3(sgrid), dim3(256), 0, r.st, A, W);
+        if (s.tail_only) tail(1, r.st, W);
+        else closest(W, 1, r.st, nullptr, W.gstack); // camera rays: path order is already coherent
+        r.g = 1, r.nin = W.P; // generation 1: one ray per path
+        return !s.tail_only && !err;
+    }
+    // wf_shade(g) at its append chunk (wf_app_chunk), then the two queue lengths to r.cnt, async
+    void shade(ChunkRun &r) {
+        WfArgs &W = r.W;
+        W.app_chunk = wf_app_chunk(W, r.nin, W.qspare ? wf_shade_blocks(num_cus, W.shade_waves) : 0u,
+                                   wf_appends_chunked(*b, mode), drv);
+        if (te && W.app_chunk) te->chunked++;
+        const int id = wf_shade_kernel(W.app_chunk, W.shade_block, W.shade_waves); // (exists for every input)
+        hipLaunchKernelGGL(shade_kernel(ShadeKernels{}, id), dim3(shade_grid(num_cus, id)), dim3(shade_desc(id).bs), 0, r.st,
+                           A, W, r.g);
+        r.dead = W.app_chunk != 0u;
+        W.app_chunk = 0u;
+        if (!(err = (int)hipMemcpyAsync(&r.cnt[0], W.cnt + WF_G + r.g, 4, hipMemcpyDeviceToHost, r.st)))
+            err = (int)hipMemcpyAsync(&r.cnt[1], W.cnt + r.g + 1, 4, hipMemcpyDeviceToHost, r.st);
+    }
+    // Generation g's traces once r.cnt holds its lengths, as wf_gen_step plans them: the sorts, closest g + 1 or the
+    // overlapped tail on the side stream beside shadow g and its resolve, the join, the tail if due.  true: shade next
+    bool trace(ChunkRun &r) {
+        const WfArgs &W = r.W;
+        const uint32_t g = r.g;
+        const WfGenStep s = wf_gen_step(g, (uint32_t)A.K, r.cnt[0], r.cnt[1], A.S.nlights, W, drv);
+        const uint32_t *order_s = s.shadow.sorted ? order_queue(W, 0, s.ns, s.shadow.bits, r.st, err) : nullptr;
+        const uint32_t *order_c = s.closest.sorted && !err ? order_queue(W, 1, s.nc, s.closest.bits, r.st, err) : nullptr;
+        const bool side = s.next || s.overlap;
+        if (err || (side && ((err = (int)hipEventRecord(r.fork, r.st)) || (err = (int)hipStreamWaitEvent(r.side, r.fork, 0)))))
+            return false;
+        WfArgs Ws = W, Wt = W;
+        Wt.gstack = W.gstack2; // (the overlapped tail's)
+        Wt.tail_shadow_gen = g;
+        if (s.next) closest(W, g + 1, r.side, order_c, W.gstack2);
+        else if (s.overlap) tail(g + 1, r.side, Wt);
+        if (err) return false;
+        Ws.order = order_s;
+        Ws.ended_only = s.ended_only ? 1u : 0u;
+        shadow_resolve(Ws, g, r.st, r.dead);
+        if (err || (side && ((err = (int)hipEventRecord(r.join, r.side)) || (err = (int)hipStreamWaitEvent(r.st, r.join, 0)))))
+            return false;
+        if (s.tail_after) tail(g + 1, r.st, W);
+        r.g = g + 1, r.nin = s.nc;
+        return !s.finished && !err;
     }
 };
 
 int launch_wavefront_chunk(const RenderArgs &A, const WfArgs &W0, int num_cus, hipStream_t st, const WfStreams &ss,
                            TraceEvents *te) {
-    WfArgs W = W0;
-    ChunkLauncher L(A, num_cus, te);
-    if (int e = L.check(W.gstride, W.tail_waves)) return e;
-    const WfBuild &b = *L.b;
-    int &err = L.err;
-    W.cam_fused = camera_fuses(b, A, W) ? 1 : 0;
-    if (!W.cam_fused) hipLaunchKernelGGL(wf_camera, dim3(L.sgrid), dim3(256), 0, st, A, W);
-    if (W.P < W.tail_min) {
-        L.tail(1, st, W, W.tail_waves);
-        return err ? err : (int)hipGetLastError();
+    ChunkLauncher L(A, num_cus, te, WF_DRIVER_CHUNK);
+    if (int e = L.check(W0)) return e;
+    uint32_t cnt[2] = {0u, 0u};
+    ChunkRun r = {W0, st, ss.side, ss.fork, ss.join, cnt};
+    for (bool more = L.start(r); more; more = L.trace(r)) { // shade, wait for the lengths, plan and trace
+        L.shade(r);
+        if (L.err || (L.err = (int)hipStreamSynchronize(st))) break;
     }
-    L.closest(W, 1, st, nullptr, W.gstack); // camera rays: path order is already coherent
-    uint32_t nin = W.P; // rays of closest queue g (generation 1: one per path)
-    for (uint32_t g = 1; g <= (uint32_t)A.K && !err; g++) {
-        W.app_chunk = wf_appends_chunked(b, L.mode) ? shade_app_chunk(W, nin, num_cus) : 0u;
-        if (te && W.app_chunk) te->chunked++;
-        launch_shade(A, W, g, num_cus, st);
-        const bool dead = W.app_chunk != 0u; // shadow queue g may hold dead entries
-        W.app_chunk = 0u;
-        uint32_t cnt[2] = {0u, 0u}; // shadow queue g, closest queue g + 1
-        if ((err = (int)hipMemcpyAsync(&cnt[0], W.cnt + WF_G + g, 4, hipMemcpyDeviceToHost, st)) ||
-            (err = (int)hipMemcpyAsync(&cnt[1], W.cnt + g + 1, 4, hipMemcpyDeviceToHost, st)) ||
-            (err = (int)hipStreamSynchronize(st)))
-            break;
-        const uint32_t nc = g < (uint32_t)A.K ? cnt[1] : 0u;
-        nin = nc;
-        const bool next = nc >= W.tail_min && nc > 0; // closest g + 1 as its own launch, beside shadow g
-        const bool pixel = !W.leaf_keys && !(W.world_keys && g >= (uint32_t)W.world_keys); // wf_shade's key choice
-        const uint32_t *order_s = (g > 1 || (W.sort_g1 & 1u)) ? order_queue(W, 0, cnt[0], st, err, pixel) : nullptr;
-        const uint32_t *order_c = (next && (g > 1 || (W.sort_g1 & 2u))) ? order_queue(W, 1, nc, st, err, pixel) : nullptr;
-        if (err) break;
-        // overlapped tail: the rest of the chunk starts beside this generation's shadow trace, tracing
-        // its own paths' shadow rays of generation g first (the paths that end at g stay with
-        // wf_trace / wf_resolve); only for scenes with lights -- a hit whose NEE query was answered
-        // without a trace (nee_skip) has no shadow ray, and the tail reads its NO_SLOT as "nothing to trace"
-        const bool overlap = !next && nc > 0 && W.tail_overlap && A.S.nlights > 0;
-        if (next || overlap) {
-            if ((err = (int)hipEventRecord(ss.fork, st)) || (err = (int)hipStreamWaitEvent(ss.side, ss.fork, 0))) break;
-            if (next) {
-                L.closest(W, g + 1, ss.side, order_c, W.gstack2);
-            } else {
-                WfArgs Wt = W;
-                Wt.gstack = W.gstack2;
-                Wt.tail_shadow_gen = g;
-                L.tail(g + 1, ss.side, Wt, W.tail_waves);
-            }
-            if (err) break;
-        }
-        W.order = order_s;
-        W.ended_only = overlap ? 1u : 0u;
-        L.shadow_resolve(W, W, g, st, dead);
-        if (err) break;
-        W.ended_only = 0u;
-        if (next || overlap)
-            if ((err = (int)hipEventRecord(ss.join, ss.side)) || (err = (int)hipStreamWaitEvent(st, ss.join, 0)))
-                break;
-        if (!next) {
-            if (nc > 0 && !overlap) L.tail(g + 1, st, W, W.tail_waves);
-            break;
-        }
-    }
-    return err ? err : (int)hipGetLastError();
+    return L.err ? L.err : (int)hipGetLastError();
 }
 
 int run_wavefront_lanes(const RenderArgs &A, WfLane *L, int nl, int num_cus, hipStream_t st, TraceEvents *te) {
-    enum { LANES_TAIL_WAVES = 4 }; // (see below)
-    ChunkLauncher K(A, num_cus, te);
+    ChunkLauncher K(A, num_cus, te, WF_DRIVER_LANES);
     for (int i = 0; i < nl; i++)
-        if (int e = K.check(L[i].W.gstride, LANES_TAIL_WAVES)) return e;
-    const WfBuild &b = *K.b;
+        if (int e = K.check(L[i].W)) return e;
     int &err = K.err;
-    struct Run {
-        WfArgs W;
-        uint32_t g = 0;
-        int phase = 0; // 0 idle, 1 shade g, 2 wait for queue lengths of g
-        bool past_camera = false;
+    struct Run : ChunkRun {
+        bool waiting = false, past_camera = false; // for the queue lengths of g; those of generation 1 have come
     } run[2];
-    // What this driver does not do, and launch_wavefront_chunk does (kept as it is): its lean tail runs at
-    // LANES_TAIL_WAVES waves per SIMD whatever "wf_tail_waves" says, generation-1 queues are sorted without consulting
-    // sort_g1, wf_shade never appends in chunks (no dead entries) and the tail is never overlapped.
-    auto tail = [&](WfLane &ln, const WfArgs &W, uint32_t g) { K.tail(g, ln.st, W, LANES_TAIL_WAVES); };
     auto shade = [&](WfLane &ln, Run &r) { // wf_shade(g), then the queue lengths to the host, async
-        launch_shade(A, r.W, r.g, num_cus, ln.st);
-        if ((err = (int)hipMemcpyAsync(&ln.hcnt[0], r.W.cnt + WF_G + r.g, 4, hipMemcpyDeviceToHost, ln.st)) ||
-            (err = (int)hipMemcpyAsync(&ln.hcnt[1], r.W.cnt + r.g + 1, 4, hipMemcpyDeviceToHost, ln.st)) ||
-            (err = (int)hipEventRecord(ln.ready, ln.st)))
-            return;
-        r.phase = 2;
-    };
-    auto start = [&](WfLane &ln, Run &r, uint32_t w0, uint32_t P) {
-        r.W = ln.W;
-        r.W.w0 = w0;
-        r.W.P = P;
-        r.g = 1;
-        r.past_camera = false;
-        if ((err = (int)hipMemsetAsync(r.W.cnt, 0, WF_CNT * sizeof(uint32_t), ln.st))) return;
-        r.W.cam_fused = camera_fuses(b, A, r.W) ? 1 : 0;
-        if (!r.W.cam_fused) hipLaunchKernelGGL(wf_camera, dim3(K.sgrid), dim3(256), 0, ln.st, A, r.W);
-        if (P < r.W.tail_min) {
-            tail(ln, r.W, 1);
-            r.phase = 0;
-            r.past_camera = true;
-            return;
-        }
-        K.closest(r.W, 1, ln.st, nullptr, r.W.gstack); // camera rays: path order is already coherent
-        if (!err) shade(ln, r);
-    };
-    // one generation's traces once its queue lengths are on the host; false: not yet
-    auto advance = [&](WfLane &ln, Run &r) -> bool {
-        const hipError_t q = hipEventQuery(ln.ready);
-        if (q == hipErrorNotReady) return false;
-        if (q != hipSuccess) {
-            err = (int)q;
-            return true;
-        }
-        r.past_camera = true;
-        const uint32_t g = r.g, ns = ln.hcnt[0];
-        const uint32_t nc = g < (uint32_t)A.K ? ln.hcnt[1] : 0u;
-        const bool next = nc >= r.W.tail_min && nc > 0;
-        const bool pixel = !r.W.leaf_keys && !(r.W.world_keys && g >= (uint32_t)r.W.world_keys); // wf_shade's key choice
-        const uint32_t *order_s = order_queue(r.W, 0, ns, ln.st, err, pixel);
-        const uint32_t *order_c = next ? order_queue(r.W, 1, nc, ln.st, err, pixel) : nullptr;
-        if (err) return true;
-        if (next) {
-            if ((err = (int)hipEventRecord(ln.fork, ln.st)) || (err = (int)hipStreamWaitEvent(ln.side, ln.fork, 0)))
-                return true;
-            K.closest(r.W, g + 1, ln.side, order_c, r.W.gstack2);
-            if (err) return true;
-        }
-        WfArgs Ws = r.W;
-        Ws.order = order_s;
-        K.shadow_resolve(Ws, r.W, g, ln.st, false);
-        if (err) return true;
-        if (next) {
-            if ((err = (int)hipEventRecord(ln.join, ln.side)) || (err = (int)hipStreamWaitEvent(ln.st, ln.join, 0)))
-                return true;
-            r.g = g + 1;
-            shade(ln, r);
-        } else {
-            if (nc > 0) tail(ln, r.W, g + 1);
-            r.phase = 0;
-        }
-        return true;
+        K.shade(r);
+        r.waiting = !err && !(err = (int)hipEventRecord(ln.ready, ln.st));
     };
     // lanes > 0 start after the work already queued on st
     for (int i = 1; i < nl && !err; i++)
@@ -1888,20 +1786,30 @@ int run_wavefront_lanes(const RenderArgs &A, WfLane *L, int nl, int num_cus, hip
     while (!err) {
         bool progress = false, busy = false;
         for (int i = 0; i < nl && !err; i++) {
-            if (run[i].phase == 0) {
+            WfLane &ln = L[i];
+            Run &r = run[i];
+            if (!r.waiting) { // idle: the next chunk, once every other lane's is past its camera trace
                 bool others_past = true;
                 for (int j = 0; j < nl; j++)
-                    if (j != i && run[j].phase != 0 && !run[j].past_camera) others_past = false;
+                    if (j != i && run[j].waiting && !run[j].past_camera) others_past = false;
                 if (next_w0 < A.n_work && others_past) {
-                    const uint32_t P = min(L[i].W.P, A.n_work - next_w0);
-                    start(L[i], run[i], next_w0, P);
-                    next_w0 += P;
+                    static_cast<ChunkRun &>(r) = {ln.W, ln.st, ln.side, ln.fork, ln.join, ln.hcnt};
+                    r.W.w0 = next_w0;
+                    r.W.P = min(ln.W.P, A.n_work - next_w0);
+                    next_w0 += r.W.P;
                     progress = true;
+                    if ((err = (int)hipMemsetAsync(r.W.cnt, 0, WF_CNT * sizeof(uint32_t), ln.st))) break;
+                    r.past_camera = !K.start(r); // (the whole chunk in wf_tail: nothing more to schedule)
+                    if (!r.past_camera) shade(ln, r);
                 }
-            } else {
-                progress = advance(L[i], run[i]) || progress;
+            } else if (const hipError_t q = hipEventQuery(ln.ready); q != hipErrorNotReady) {
+                // the queue lengths are on the host: this generation's traces, then the next wf_shade
+                r.past_camera = progress = true;
+                r.waiting = false;
+                if (q != hipSuccess) err = (int)q;
+                else if (K.trace(r)) shade(ln, r);
             }
-            busy = busy || run[i].phase != 0;
+            busy = busy || r.waiting;
         }
         if (!busy && next_w0 >= A.n_work) break;
         if (!progress) std::this_thread::yield();

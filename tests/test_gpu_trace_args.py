@@ -21,7 +21,7 @@ SIZES = {"sponza": (80, 45, 4), "nanobox": (64, 36, 2)}
 BUILD = {"sponza": 59, "nanobox": 44}
 # ctx.hpp defaults of the options the cases change (Pair sets wf_tail_min 0)
 DEFAULTS = {"wf_vis_mark": 1, "wf_vis_dw": 1, "wf_tail_overlap": 0, "wf_tail_min": 0, "wf_xcd": 7, "wf_sort": -1,
-            "wf_sort_min": 1 << 20, "wf_app_chunk": 0, "wf_lanes": 1}
+            "wf_sort_min": 1 << 20, "wf_app_chunk": 0, "wf_lanes": 1, "wf_sort_g1": 3, "wf_tail_waves": 4}
 
 
 class Case:
@@ -42,9 +42,10 @@ def cases(ca, po, scenes):
     return {name: Case(ca, po, scenes, name) for name in SIZES}
 
 
-def check(ca, case, options, what):
+def check(ca, case, options, what, stats=None):
     """Counting and lean renders with `options` set: both equal the oracle's frame, the counting build's
-    counters the oracle's, the lean build's per-query counters the counting build's."""
+    counters the oracle's, the lean build's per-query counters the counting build's.  stats (a list): gets each
+    of the two renders' (chunked wf_shade launches, trace launches per kind)."""
     dev = case.pair.dev
     dev.set_option("kernel", 2)
     p = ca.render_params(case.x, case.y, case.s, K, SEED)
@@ -53,9 +54,14 @@ def check(ca, case, options, what):
             dev.set_option(key, v)
         g = dev.render(case.cam, p)
         gc = dev.counters()
+        launches = lambda: {kind: v["launches"] for kind, v in dev.trace_stats().items()}
+        if stats is not None:
+            stats.append((dev.chunked_shades(), launches()))
         dev.set_option("counters", 0)
         g_lean = dev.render(case.cam, p)
         lc = dev.counters()
+        if stats is not None:
+            stats.append((dev.chunked_shades(), launches()))
         build = dev.last_trace_build()
         chunked = dev.chunked_shades()
     finally:
@@ -100,6 +106,21 @@ def test_point_of_use_argument_branches(ca, cases, scene, options):
     chunked = check(ca, cases[scene], options, str(options))
     if "wf_app_chunk" in options:
         assert chunked > 0, "the lean render used no chunked appends"
+
+
+@pytest.mark.parametrize("scene", ["sponza", "nanobox"])
+def test_lanes_driver_keeps_its_policy(ca, cases, scene):
+    """run_wavefront_lanes ignores wf_sort_g1, never appends in chunks, never overlaps the tail and runs its lean
+    tail at 4 waves per SIMD (wfgen.hpp WF_DRIVER_LANES): with those four options set against it, the same
+    launches and the same bits."""
+    lanes = {"wf_lanes": 2, "wf_tail_min": 3000}
+    against = dict(lanes, wf_app_chunk=256, wf_sort_g1=0, wf_tail_overlap=1, wf_tail_waves=6)
+    plain, opposed = [], []
+    check(ca, cases[scene], lanes, str(lanes), plain)
+    check(ca, cases[scene], against, str(against), opposed)
+    assert [c for c, _ in plain + opposed] == [0, 0, 0, 0], (plain, opposed)
+    assert [l for _, l in plain] == [l for _, l in opposed], (plain, opposed)
+    assert sum(plain[1][1].values()) > 0
 
 
 @pytest.mark.parametrize("scene", ["sponza", "nanobox"])
