@@ -4,7 +4,7 @@
 // kernels.hip header), the progressive accumulator, the counters and the
 // per-launch HIP events.  No C++ exception or hipError_t crosses the ABI.
 #include "ctx.hpp"
-#include "leafcull.hpp"
+#include "scenelayout.hpp"
 #include "wfplan.hpp"
 
 #include <algorithm>
@@ -25,9 +25,14 @@ int hip_fail(cr_ctx *c, hipError_t e, const char *what) {
     return fail(c, CR_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
 
+int enter(cr_ctx *c, bool set_device) {
+    if (!c) return CR_E_INVALID;
+    if (c->device < 0) return fail(c, CR_E_HIP, c->err.empty() ? "no device" : c->err);
+    if (set_device) HIPCHK(hipSetDevice(c->device));
+    return CR_OK;
+}
 
 void free_scene(cr_ctx *c) {
-    for (void *p : c->scene_bufs) hipFree(p);
     c->scene_bufs.clear();
     c->has_scene = false;
     c->S = cr::DevScene{};
@@ -36,17 +41,16 @@ void free_scene(cr_ctx *c) {
 }
 
 template <class T> int upload(cr_ctx *c, const std::vector<T> &h, const T **out) {
-    void *d = nullptr;
-    size_t bytes = h.size() * sizeof(T);
-    if (bytes == 0) bytes = 16;
-    hipError_t e = hipMalloc(&d, bytes);
+    crx::DevBuf d;
+    d.cap = h.empty() ? 16 : h.size() * sizeof(T);
+    hipError_t e = hipMalloc(&d.ptr, d.cap);
     if (e != hipSuccess) return fail(c, CR_E_OOM, std::string("hipMalloc: ") + hipGetErrorString(e));
-    c->scene_bufs.push_back(d);
+    *out = d.as<const T>();
+    c->scene_bufs.push_back(std::move(d));
     if (!h.empty()) {
-        e = hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
+        e = hipMemcpy((void *)*out, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
         if (e != hipSuccess) return hip_fail(c, e, "hipMemcpy(scene)");
     }
-    *out = (const T *)d;
     return CR_OK;
 }
 
@@ -65,14 +69,8 @@ int check_params(cr_ctx *c, const cr_render_params *p) {
 uint32_t tile_of(const cr_render_params *p) { return p->tile ? p->tile : 32u; }
 
 // Grow-only device work buffer.
-int grow(cr_ctx *c, void **buf, size_t &cap, size_t need) {
-    if (need <= cap && *buf) return CR_OK;
-    if (*buf) hipFree(*buf);
-    *buf = nullptr;
-    cap = 0;
-    if (hipMalloc(buf, need ? need : 16) != hipSuccess) return fail(c, CR_E_OOM, "work buffer");
-    cap = need;
-    return CR_OK;
+int grow(cr_ctx *c, DevBuf &b, size_t need, const char *label) {
+    return b.grow(need) ? fail(c, CR_E_OOM, label) : CR_OK;
 }
 
 using cr::LEAF_CULL_MIN_TRIS; // (wfbuilds.hpp: scenes below it default to the build without the leaf cull)
@@ -131,7 +129,7 @@ void fill_args(cr_ctx *c, cr::RenderArgs &A, const cr_camera *cam, const cr_rend
     A.stack_depth = c->stack_depth;
     A.mode = mode;
     A.out = out;
-    A.counters = c->d_counters;
+    A.counters = c->d_counters.as<unsigned long long>();
     A.full_counters = c->full_counters;
     A.perf_counters = c->perf_counters;
     A.diag_kinds = c->diag_kinds;
@@ -180,7 +178,7 @@ uint64_t wf_path_cap(cr_ctx *c, int k) {
     if (!c->wf_mem_budget) {
         size_t freeb = 0, totalb = 0;
         if (hipMemGetInfo(&freeb, &totalb) != hipSuccess) return ~0ull;
-        c->wf_mem_budget = freeb + c->wf_bytes + c->wf2_bytes;
+        c->wf_mem_budget = freeb + c->d_wf.cap + c->d_wf2.cap;
     }
     return cr::wf_path_cap_of(c->wf_mem_budget, k, cr::wf_chunked(*c, c->n_tris));
 }
@@ -218,7 +216,7 @@ int run_render(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, float
         return fail(c, CR_E_INVALID, "perf_counters: the wavefront kernel's trace builds " + cr::wf_perf_builds_text() +
                                          " only, without the counting build");
     c->last_build = c->kernel == 2 ? (c->full_counters ? -1 : A.variant) : -2;
-    HIPCHK(hipMemsetAsync(c->d_counters, 0, cr::CTR_SLOTS * sizeof(unsigned long long), st));
+    HIPCHK(hipMemsetAsync(c->d_counters.ptr, 0, cr::CTR_SLOTS * sizeof(unsigned long long), st));
     uint32_t blk, blocks;
     cr::wf_trace_geometry(c->full_counters ? -1 : A.variant, c->num_cus, blk, blocks);
     A.gstride = blk * blocks;
@@ -230,38 +228,39 @@ int run_render(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, float
     const cr::WfPlan pl = cr::wf_plan(in);
     if (pl.code) return fail(c, pl.code, pl.msg);
     const int lanes = c->wf_lanes;
-    if (int r = grow(c, &c->d_gstack, c->gstack_bytes, pl.gstack_bytes)) return r;
-    if (int r = grow(c, &c->d_samples, c->samples_bytes, pl.samples_bytes)) return r;
+    if (int r = grow(c, c->d_gstack, pl.gstack_bytes)) return r;
+    if (int r = grow(c, c->d_samples, pl.samples_bytes)) return r;
     if (pl.chunked)
-        if (int r = grow(c, &c->d_run, c->run_bytes, pl.run_bytes)) return r;
+        if (int r = grow(c, c->d_run, pl.run_bytes)) return r;
     if (pl.chunked && m2)
-        if (int r = grow(c, &c->d_run2, c->run2_bytes, pl.run_bytes)) return r;
-    if (int r = grow(c, &c->d_wf, c->wf_bytes, pl.need_alloc)) return r;
+        if (int r = grow(c, c->d_run2, pl.run_bytes)) return r;
+    if (int r = grow(c, c->d_wf, pl.need_alloc)) return r;
     if (lanes == 2)
-        if (int r = grow(c, &c->d_wf2, c->wf2_bytes, pl.need_alloc)) return r;
-    A.gstack = (uint2 *)c->d_gstack;
-    A.samples = (float *)c->d_samples;
-    A.run = (float *)c->d_run;
+        if (int r = grow(c, c->d_wf2, pl.need_alloc)) return r;
+    A.gstack = c->d_gstack.as<uint2>();
+    A.samples = c->d_samples.as<float>();
+    A.run = c->d_run.as<float>();
     cr::WfArgs W{};
     cr::WfArgs W2{};
-    cr::wf_bind(in, pl, c->d_wf, A.gstack, 0, W);
-    if (lanes == 2) cr::wf_bind(in, pl, c->d_wf2, A.gstack, 1, W2);
+    cr::wf_bind(in, pl, c->d_wf.ptr, A.gstack, 0, W);
+    if (lanes == 2) cr::wf_bind(in, pl, c->d_wf2.ptr, A.gstack, 1, W2);
     // screen-space cull boxes of this camera for the camera-ray trace (camcull.hpp),
     // computed inside the timed region of every render
     // (built for triangle-less scenes too: the culling kernels read them unconditionally, and
     // with n_refs + 4 empty boxes every sample is outside)
     const bool cull = !c->full_counters && cr::wf_variant_culls(A.variant);
     if (cull) {
-        if (int r = grow(c, &c->d_cull, c->cull_bytes, 16 * ((size_t)c->n_refs + 4))) return r;
-        if (int r = grow(c, &c->d_cull_node, c->cull_node_bytes, 16 * (size_t)c->S.n_nodes)) return r;
+        if (int r = grow(c, c->d_cull, 16 * ((size_t)c->n_refs + 4))) return r;
+        if (int r = grow(c, c->d_cull_node, 16 * (size_t)c->S.n_nodes)) return r;
     }
-    A.cull = cull ? (const float4 *)c->d_cull : nullptr;
-    A.cull_node = cull ? (const float4 *)c->d_cull_node : nullptr;
+    A.cull = cull ? c->d_cull.as<const float4>() : nullptr;
+    A.cull_node = cull ? c->d_cull_node.as<const float4>() : nullptr;
+    const cr::WfStreams wfs{c->side, c->fork, c->join};
     c->tev.n = 0;
     c->tev.chunked = 0;
     HIPCHK(hipEventRecord(c->ev0, st));
     if (cull)
-        if (int e = cr::launch_cam_cull(A, c->n_refs, (float4 *)c->d_cull, (float4 *)c->d_cull_node, c->d_levels,
+        if (int e = cr::launch_cam_cull(A, c->n_refs, c->d_cull.as<float4>(), c->d_cull_node.as<float4>(), c->d_levels,
                                         (const uint32_t(*)[2])c->levels.data(), (int)c->levels.size(), st))
             return hip_fail(c, (hipError_t)e, "cull-box kernel launch");
     for (uint32_t s0 = 0; s0 < pl.spp_pass; s0 += (uint32_t)pl.chunk) {
@@ -270,8 +269,8 @@ int run_render(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, float
         A.n_work = A.n_items * A.s_count;
         int e = 0;
         if (lanes == 2) {
-            cr::WfLane L[2] = {{W, st, c->wfs.side, c->wfs.fork, c->wfs.join, c->lane_ev[0], c->hcnt},
-                               {W2, c->stream2, c->side2, c->fork2, c->join2, c->lane_ev[1], c->hcnt + 2}};
+            cr::WfLane L[2] = {{W, st, c->side, c->fork, c->join, c->lane_ev[0], c->hcnt.words()},
+                               {W2, c->stream2, c->side2, c->fork2, c->join2, c->lane_ev[1], c->hcnt.words() + 2}};
             e = cr::run_wavefront_lanes(A, L, 2, c->num_cus, st, &c->tev);
         } else {
             const uint32_t P = W.P;
@@ -279,17 +278,17 @@ int run_render(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, float
                 W.w0 = w0;
                 W.P = std::min(P, A.n_work - w0);
                 HIPCHK(hipMemsetAsync(W.cnt, 0, cr::WF_CNT * sizeof(uint32_t), st));
-                e = cr::launch_wavefront_chunk(A, W, c->num_cus, st, c->wfs, &c->tev);
+                e = cr::launch_wavefront_chunk(A, W, c->num_cus, st, wfs, &c->tev);
             }
             W.P = P;
         }
         if (!e) e = cr::launch_sum_samples(A, s0 == 0, s0 + A.s_count == pl.spp_pass, st, c->sum_lds, c->sum_staged != 0,
-                                            m2, (float *)c->d_run2);
+                                            m2, c->d_run2.as<float>());
         if (e) return hip_fail(c, (hipError_t)e, "render kernel launch");
     }
     HIPCHK(hipEventRecord(c->ev1, st));
     unsigned long long h[cr::CTR_SLOTS];
-    HIPCHK(hipMemcpyAsync(h, c->d_counters, sizeof(h), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(h, c->d_counters.ptr, sizeof(h), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1));
     c->last = counters_of(h);
@@ -318,404 +317,13 @@ int run_render(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, float
 
 using namespace crx;
 
-extern "C" {
-
-cr_ctx *cr_create(int device) {
-    cr_ctx *c = new cr_ctx();
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
-        c->err = "no HIP device";
-        return c; // error surfaced on first use; cr_last_error explains
-    }
-    if (device < 0 || device >= n) {
-        c->err = "bad device index";
-        return c;
-    }
-    c->device = device;
-    if (hipSetDevice(device) != hipSuccess) {
-        c->err = "hipSetDevice failed";
-        c->device = -1;
-        return c;
-    }
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->num_cus = prop.multiProcessorCount;
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipStreamCreateWithFlags(&c->wfs.side, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&c->wfs.fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->wfs.join, hipEventDisableTiming) != hipSuccess ||
-        hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking) != hipSuccess ||
-        hipStreamCreateWithFlags(&c->side2, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&c->fork2, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->join2, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->lane_ev[0], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->lane_ev[1], hipEventDisableTiming) != hipSuccess ||
-        hipHostMalloc((void **)&c->hcnt, 4 * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess ||
-        hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
-        hipEventCreateWithFlags(&c->q_ev, hipEventDisableTiming) != hipSuccess ||
-        hipMalloc(&c->d_counters, cr::CTR_SLOTS * sizeof(unsigned long long)) != hipSuccess) {
-        c->err = "device init failed";
-        c->device = -1;
-    }
-    return c;
+// An accumulator (d_accum, or the moment accumulator d_accum2 beside it) at `elems` floats: reallocated when a frame
+// of another size arrives (zero: a render starts a new accumulation; cr_set_*accumulator overwrite it anyway)
+static int size_accumulator(cr_ctx *c, DevBuf &acc, const char *label, size_t elems, bool zero) {
+    hipError_t e = hipSuccess;
+    const int rc = acc.resize_exact(elems * sizeof(float), zero, &e);
+    return rc == CR_E_OOM ? fail(c, rc, label) : rc ? hip_fail(c, e, "hipMemset(accumulator)") : CR_OK;
 }
-
-void cr_destroy(cr_ctx *c) {
-    if (!c) return;
-    if (c->device >= 0) {
-        hipSetDevice(c->device);
-        release_dist(c);
-        free_scene(c);
-        if (c->d_accum) hipFree(c->d_accum);
-        if (c->d_gstack) hipFree(c->d_gstack);
-        if (c->d_samples) hipFree(c->d_samples);
-        if (c->d_run) hipFree(c->d_run);
-        if (c->d_accum2) hipFree(c->d_accum2);
-        if (c->d_run2) hipFree(c->d_run2);
-        if (c->d_err) hipFree(c->d_err);
-        if (c->d_nstats) hipFree(c->d_nstats);
-        if (c->d_wf) hipFree(c->d_wf);
-        if (c->d_cull) hipFree(c->d_cull);
-        if (c->d_cull_node) hipFree(c->d_cull_node);
-        if (c->d_counters) hipFree(c->d_counters);
-        if (c->ev0) hipEventDestroy(c->ev0);
-        for (int i = 0; i < 2 * c->tev.cap; i++) hipEventDestroy(c->tev.ev[i]);
-        delete[] c->tev.ev;
-        delete[] c->tev.kind;
-        if (c->ev1) hipEventDestroy(c->ev1);
-        if (c->stream) hipStreamDestroy(c->stream);
-        if (c->wfs.side) hipStreamDestroy(c->wfs.side);
-        if (c->wfs.fork) hipEventDestroy(c->wfs.fork);
-        if (c->wfs.join) hipEventDestroy(c->wfs.join);
-        if (c->stream2) hipStreamDestroy(c->stream2);
-        if (c->side2) hipStreamDestroy(c->side2);
-        if (c->fork2) hipEventDestroy(c->fork2);
-        if (c->join2) hipEventDestroy(c->join2);
-        for (hipEvent_t e : c->lane_ev)
-            if (e) hipEventDestroy(e);
-        if (c->hcnt) hipHostFree(c->hcnt);
-        if (c->d_wf2) hipFree(c->d_wf2);
-        if (c->q_pending) hipEventSynchronize(c->q_ev);
-        if (c->d_query) hipFree(c->d_query);
-        if (c->q_ev) hipEventDestroy(c->q_ev);
-    }
-    delete c;
-}
-
-const char *cr_last_error(cr_ctx *c) { return c ? c->err.c_str() : "null context"; }
-
-int cr_upload_scene(cr_ctx *c, const cr_scene_desc *d) {
-    if (!c) return CR_E_INVALID;
-    if (c->device < 0) return fail(c, CR_E_HIP, c->err.empty() ? "no device" : c->err);
-    if (!d || !d->nodes || d->n_nodes == 0) return fail(c, CR_E_INVALID, "empty kd tree");
-    if (d->n_tris && (!d->tri_pos || !d->tri_normal || !d->tri_kd || !d->tri_ke || !d->tri_uv))
-        return fail(c, CR_E_INVALID, "missing triangle arrays");
-    if (d->max_depth > 256) return fail(c, CR_E_DEPTH, "kd tree deeper than 256");
-    HIPCHK(hipSetDevice(c->device));
-    free_scene(c);
-    // a new scene re-queries the path budget at its first plan (wf_path_cap): buffers grown since the last
-    // query (gather and tile buffers, the caller's own tensors) must not leave the chunk cap above the HBM
-    // that is free now.  Ranks still agree on a group's plan: plan_layers' all-reduce MIN, and the per-group
-    // agreement of cr_render_dist_layers_device / cr_group_render_layers
-    c->wf_mem_budget = 0;
-    const uint32_t nt = d->n_tris;
-    // nodes -> {split bits | first, axis | child<<2}, validated first
-    const uint32_t NN = d->n_nodes;
-    for (uint32_t i = 0; i < NN; i++) {
-        const cr_kdnode &n = d->nodes[i];
-        if (n.axis == 3) {
-            if (n.count >= (1u << 30) || (uint64_t)n.child_or_first + n.count > d->n_refs)
-                return fail(c, CR_E_INVALID, "bad leaf range");
-        } else if (n.axis > 2 || (uint64_t)n.child_or_first + 1 >= NN || n.child_or_first >= (1u << 30)) {
-            return fail(c, CR_E_INVALID, "bad inner node");
-        }
-    }
-    // node numbering: the first NODE_BFS nodes breadth-first from the root (each inner
-    // node's two children take consecutive ids, as KDTree::build allocates them), the
-    // rest in the reference's depth-first order -- the top of the tree is nodes
-    // 0..NODE_BFS-1 for the LDS node tile; only addresses change, not the traversal
-    std::vector<uint32_t> newid(NN, 0xffffffffu), order;
-    order.reserve(NN);
-    order.push_back(0);
-    newid[0] = 0;
-    for (size_t h = 0; h < order.size() && order.size() + 2 <= c->node_bfs; h++) {
-        const cr_kdnode &n = d->nodes[order[h]];
-        if (n.axis == 3) continue;
-        for (uint32_t k = 0; k < 2; k++) {
-            const uint32_t ch = n.child_or_first + k;
-            if (newid[ch] != 0xffffffffu) return fail(c, CR_E_INVALID, "kd node with two parents");
-            newid[ch] = (uint32_t)order.size();
-            order.push_back(ch);
-        }
-    }
-    for (uint32_t i = 0; i < NN; i++)
-        if (newid[i] == 0xffffffffu) {
-            newid[i] = (uint32_t)order.size();
-            order.push_back(i);
-        }
-    std::vector<uint2> nodes(NN);
-    for (uint32_t i = 0; i < NN; i++) {
-        const cr_kdnode &n = d->nodes[i];
-        if (n.axis == 3) {
-            nodes[newid[i]] = make_uint2(n.child_or_first, 3u | (n.count << 2));
-        } else {
-            const uint32_t ch = newid[n.child_or_first];
-            if (newid[n.child_or_first + 1] != ch + 1) return fail(c, CR_E_INVALID, "kd siblings not adjacent");
-            uint32_t sb;
-            std::memcpy(&sb, &n.split, 4);
-            nodes[newid[i]] = make_uint2(sb, n.axis | (ch << 2));
-        }
-    }
-    // fat node records: a node's own record followed by both children's
-    if ((uint64_t)32 * d->n_nodes > 0xFFFFFFFFull) return fail(c, CR_E_INVALID, "more than 134 M kd nodes");
-    std::vector<uint4> fat((size_t)2 * d->n_nodes, make_uint4(0u, 0u, 0u, 0u));
-    for (uint32_t i = 0; i < d->n_nodes; i++) {
-        const uint2 n = nodes[i];
-        fat[2 * (size_t)i].x = n.x;
-        fat[2 * (size_t)i].y = n.y;
-        if ((n.y & 3u) != 3u) {
-            const uint32_t ch = n.y >> 2;
-            fat[2 * (size_t)i].z = nodes[ch].x;
-            fat[2 * (size_t)i].w = nodes[ch].y;
-            fat[2 * (size_t)i + 1] = make_uint4(nodes[ch + 1].x, nodes[ch + 1].y, 0u, 0u);
-        }
-    }
-    // leaf-ordered triangle records {A,id},{B-A},{C-A}: e1/e2 computed exactly as
-    // intersectRayTriangle does each time (kdtree.cpp:222-223), so bit-identical.
-    // load_rec addresses records with a 32-bit byte offset
-    if ((uint64_t)16 * cr::REC_STRIDE * ((uint64_t)d->n_refs + 1) > 0xFFFFFFFFull)
-        return fail(c, CR_E_INVALID, "more than 89 M leaf references (triangle records exceed 4 GiB)");
-    // + one zero record past the last (an empty leaf's `first` may be n_refs)
-    std::vector<float4> recs((size_t)cr::REC_STRIDE * ((size_t)d->n_refs + 1), make_float4(0.f, 0.f, 0.f, 0.f));
-    for (uint32_t r = 0; r < d->n_refs; r++) {
-        const uint32_t t = d->refs[r];
-        if (t >= nt) return fail(c, CR_E_INVALID, "leaf ref out of range");
-        const float *p = d->tri_pos + 9 * (size_t)t;
-        float idf;
-        std::memcpy(&idf, &t, 4);
-        float4 *q = recs.data() + (size_t)cr::REC_STRIDE * r;
-        q[0] = make_float4(p[0], p[1], p[2], idf);
-        q[1] = make_float4(p[3] - p[0], p[4] - p[1], p[5] - p[2], 0.f);
-        q[2] = make_float4(p[6] - p[0], p[7] - p[1], p[8] - p[2], 0.f);
-    }
-    // leaf cull records (leafcull.hpp), per node of the new numbering; host threads.  The per-ray and
-    // fixed-pad forms stay on the host: they are the steps from which the packed (LC 4) and the
-    // compressed (LC 5) records the traces read are derived
-    std::vector<float4> lcull((size_t)cr::LC_REC * NN, make_float4(0.f, 0.f, 0.f, 0.f));
-    {
-        const unsigned nth = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-        std::vector<std::thread> th;
-        for (unsigned w = 0; w < nth; w++)
-            th.emplace_back([&, w] {
-                float A[cr::LC_MAXREFS][3], e1[cr::LC_MAXREFS][3], e2[cr::LC_MAXREFS][3];
-                for (uint32_t i = w; i < NN; i += nth) {
-                    if ((nodes[i].y & 3u) != 3u) continue;
-                    const uint32_t first = nodes[i].x, cnt = nodes[i].y >> 2;
-                    const uint32_t m = std::min(cnt, (uint32_t)cr::LC_MAXREFS);
-                    for (uint32_t j = 0; j < m; j++) {
-                        const float4 *q = recs.data() + (size_t)cr::REC_STRIDE * (first + j);
-                        A[j][0] = q[0].x, A[j][1] = q[0].y, A[j][2] = q[0].z;
-                        e1[j][0] = q[1].x, e1[j][1] = q[1].y, e1[j][2] = q[1].z;
-                        e2[j][0] = q[2].x, e2[j][1] = q[2].y, e2[j][2] = q[2].z;
-                    }
-                    cr::leaf_cull_record(A, e1, e2, cnt, (cr::LcFloat4 *)(lcull.data() + (size_t)cr::LC_REC * i));
-                }
-            });
-        for (auto &t : th) t.join();
-    }
-    // ... and in the fixed-pad form: origins and vertices inside the padded box (+1: the 0.001 n offsets)
-    std::vector<float4> lcullf((size_t)cr::LC_REC * NN, make_float4(0.f, 0.f, 0.f, 0.f));
-    double lc_db = 1.0;
-    {
-        double &db = lc_db, smax = 0.0;
-        for (int i = 0; i < 3; i++) {
-            db = std::max(db, std::max(std::fabs((double)d->box_min[i]), std::fabs((double)d->box_max[i])) + 1.0);
-            smax = std::max(smax, (double)d->box_max[i] - (double)d->box_min[i] + 2.0);
-        }
-        db *= 1.0001;
-        for (uint32_t i = 0; i < NN; i++)
-            cr::leaf_cull_fixed((const cr::LcFloat4 *)(lcull.data() + (size_t)cr::LC_REC * i), db, smax,
-                                (cr::LcFloat4 *)(lcullf.data() + (size_t)cr::LC_REC * i));
-    }
-    std::vector<float4> lcullp((size_t)cr::LC_RECP * NN, make_float4(0.f, 0.f, 0.f, 0.f));
-    for (uint32_t i = 0; i < NN; i++)
-        cr::leaf_cull_pack((const cr::LcFloat4 *)(lcullf.data() + (size_t)cr::LC_REC * i),
-                           (nodes[i].y & 3u) == 3u ? nodes[i].y >> 2 : 0u,
-                           (cr::LcFloat4 *)(lcullp.data() + (size_t)cr::LC_RECP * i));
-    // ... and compressed on the scene's grid (48 B per node, LC 5)
-    cr::LcGrid lcg = cr::lc_grid_make((const cr::LcFloat4 *)lcullf.data(), NN, lc_db);
-    cr::lc_grid_dt(lcg, (const cr::LcFloat4 *)lcullf.data(), NN);
-    std::vector<uint4> lcullc((size_t)cr::LC_RECC * NN, make_uint4(0u, 0u, 0u, 0u));
-    for (uint32_t i = 0; i < NN; i++)
-        cr::leaf_cull_compress((const cr::LcFloat4 *)(lcull.data() + (size_t)cr::LC_REC * i),
-                               (const cr::LcFloat4 *)(lcullf.data() + (size_t)cr::LC_REC * i),
-                               (nodes[i].y & 3u) == 3u ? nodes[i].y >> 2 : 0u, lcg,
-                               (uint32_t *)(lcullc.data() + (size_t)cr::LC_RECC * i));
-    std::vector<float4> tri((size_t)3 * nt), mn(nt), mkd(nt), mke(nt);
-    std::vector<float2> muv((size_t)3 * nt);
-    for (uint32_t t = 0; t < nt; t++) {
-        const float *p = d->tri_pos + 9 * (size_t)t;
-        for (int v = 0; v < 3; v++) tri[3 * (size_t)t + v] = make_float4(p[3 * v], p[3 * v + 1], p[3 * v + 2], 0.f);
-        const uint32_t em = d->tri_emissive ? (d->tri_emissive[t] ? 1u : 0u)
-                                            : ((d->tri_ke[3 * t] > 0.f || d->tri_ke[3 * t + 1] > 0.f ||
-                                                d->tri_ke[3 * t + 2] > 0.f) ? 1u : 0u);
-        float emf;
-        std::memcpy(&emf, &em, 4);
-        mn[t] = make_float4(d->tri_normal[3 * t], d->tri_normal[3 * t + 1], d->tri_normal[3 * t + 2], emf);
-        int32_t ti = d->tri_tex ? d->tri_tex[t] : -1;
-        if (ti >= (int32_t)d->n_textures) return fail(c, CR_E_INVALID, "texture index out of range");
-        float tif;
-        std::memcpy(&tif, &ti, 4);
-        mkd[t] = make_float4(d->tri_kd[3 * t], d->tri_kd[3 * t + 1], d->tri_kd[3 * t + 2], tif);
-        mke[t] = make_float4(d->tri_ke[3 * t], d->tri_ke[3 * t + 1], d->tri_ke[3 * t + 2], 0.f);
-        for (int v = 0; v < 3; v++)
-            muv[3 * (size_t)t + v] = make_float2(d->tri_uv[6 * t + 2 * v], d->tri_uv[6 * t + 2 * v + 1]);
-    }
-    std::vector<uint2> lights(d->n_lights);
-    for (uint32_t i = 0; i < d->n_lights; i++) {
-        if (d->light_id[i] >= nt) return fail(c, CR_E_INVALID, "light id out of range");
-        uint32_t sb;
-        std::memcpy(&sb, &d->light_surface[i], 4);
-        lights[i] = make_uint2(d->light_id[i], sb);
-    }
-    std::vector<uint4> texs(d->n_textures);
-    std::vector<uint8_t> texels;
-    for (uint32_t i = 0; i < d->n_textures; i++) {
-        const cr_texture &t = d->textures[i];
-        if (t.width <= 0 || t.height <= 0 || t.components <= 0 || !t.data)
-            return fail(c, CR_E_INVALID, "bad texture");
-        size_t off = (texels.size() + 15) & ~(size_t)15;
-        size_t bytes = (size_t)t.width * t.height * t.components;
-        texels.resize(off + bytes + cr::tex_pad(t.width, t.components), 0);
-        std::memcpy(texels.data() + off, t.data, bytes);
-        if (off > 0xffffffffull) return fail(c, CR_E_INVALID, "texture atlas > 4 GiB");
-        texs[i] = make_uint4((uint32_t)t.width, (uint32_t)t.height, (uint32_t)t.components, (uint32_t)off);
-    }
-    // inner nodes grouped by depth, deepest level first (children have larger ids than
-    // their parent in this numbering: one forward pass gives the depths)
-    std::vector<uint32_t> depth(NN, 0), levels;
-    std::vector<std::pair<uint32_t, uint32_t>> level_off;
-    uint32_t tree_depth = 0; // deepest node (root = 0): the most entries a traversal stack holds
-    {
-        uint32_t maxd = 0;
-        for (uint32_t i = 0; i < NN; i++) {
-            tree_depth = std::max(tree_depth, depth[i]);
-            if ((nodes[i].y & 3u) == 3u) continue;
-            const uint32_t ch = nodes[i].y >> 2;
-            if (ch <= i) return fail(c, CR_E_INVALID, "kd child numbered before its parent");
-            depth[ch] = depth[ch + 1] = depth[i] + 1;
-            maxd = std::max(maxd, depth[i]);
-        }
-        // the stacks (LDS rings, gstack, the packet trace's PACKET_DEPTH node stack) are sized
-        // from the tree itself, never from the caller's declared max_depth
-        if (tree_depth > 256) return fail(c, CR_E_DEPTH, "kd tree deeper than 256");
-        std::vector<uint32_t> cnt(maxd + 1, 0);
-        for (uint32_t i = 0; i < NN; i++)
-            if ((nodes[i].y & 3u) != 3u) cnt[depth[i]]++;
-        uint32_t off = 0;
-        for (int dd = (int)maxd; dd >= 0; dd--) {
-            level_off.emplace_back(off, cnt[dd]);
-            off += cnt[dd];
-        }
-        levels.resize(off);
-        std::vector<uint32_t> pos(maxd + 1);
-        for (uint32_t dd = 0; dd <= maxd; dd++) pos[dd] = level_off[maxd - dd].first;
-        for (uint32_t i = 0; i < NN; i++)
-            if ((nodes[i].y & 3u) != 3u) levels[pos[depth[i]]++] = i;
-    }
-    const uint32_t *levels_dev = nullptr;
-    int rc;
-    if ((rc = upload(c, levels, &levels_dev))) {
-        free_scene(c);
-        return rc;
-    }
-    if ((rc = upload(c, nodes, &c->S.nodes)) || (rc = upload(c, fat, &c->S.fat)) || (rc = upload(c, recs, &c->S.recs)) ||
-        (rc = upload(c, lcullp, &c->S.lcullp)) || (rc = upload(c, lcullc, &c->S.lcullc)) || (rc = upload(c, tri, &c->S.tri)) ||
-        (rc = upload(c, mn, &c->S.mat_n)) || (rc = upload(c, mkd, &c->S.mat_kd)) || (rc = upload(c, mke, &c->S.mat_ke)) ||
-        (rc = upload(c, muv, &c->S.mat_uv)) || (rc = upload(c, lights, &c->S.lights)) ||
-        (rc = upload(c, texs, &c->S.texs)) || (rc = upload(c, texels, &c->S.texels))) {
-        free_scene(c);
-        return rc;
-    }
-    c->S.lcg = lcg;
-    c->S.nlights = d->n_lights;
-    c->S.n_nodes = d->n_nodes;
-    c->S.bmin = make_float3(d->box_min[0], d->box_min[1], d->box_min[2]);
-    c->S.bmax = make_float3(d->box_max[0], d->box_max[1], d->box_max[2]);
-    {
-        double db = 1.0; // every origin (a hit point + 0.001 n) and vertex lies in the padded box
-        for (int i = 0; i < 3; i++)
-            db = std::max(db, std::max(std::fabs((double)d->box_min[i]), std::fabs((double)d->box_max[i])) + 1.0);
-        c->S.db = (float)(db * 1.0001);
-    }
-    c->stack_depth = std::max(tree_depth, std::max(d->max_depth, 1u));
-    c->n_refs = d->n_refs;
-    c->n_tris = d->n_tris;
-    for (int a = 0; a < 3; a++) c->splits[a].clear();
-    for (uint32_t i = 0; i < NN; i++)
-        if (d->nodes[i].axis < 3) c->splits[d->nodes[i].axis].push_back(d->nodes[i].split);
-    for (int a = 0; a < 3; a++) std::sort(c->splits[a].begin(), c->splits[a].end());
-    c->d_levels = levels_dev;
-    c->levels = std::move(level_off);
-    c->has_scene = true;
-    return CR_OK;
-}
-
-int cr_tile_origin(const cr_render_params *p, uint32_t rank, uint32_t local, uint32_t *x0, uint32_t *y0) {
-    if (!p || !x0 || !y0 || local >= cr_tiles_for_rank(p, rank)) return CR_E_INVALID;
-    const uint32_t T = tile_of(p), tx = (p->xres + T - 1) / T, s = rank + local * p->nranks;
-    *x0 = cr::tile_slot_column(s, tx, p->nranks) * T;
-    *y0 = s / tx * T;
-    return CR_OK;
-}
-
-uint32_t cr_tiles_for_rank(const cr_render_params *p, uint32_t rank) {
-    if (!p || p->nranks == 0 || rank >= p->nranks || p->xres == 0 || p->yres == 0) return 0;
-    const uint32_t T = tile_of(p);
-    const uint32_t nt = ((p->xres + T - 1) / T) * ((p->yres + T - 1) / T);
-    return nt > rank ? (nt - rank + p->nranks - 1) / p->nranks : 0;
-}
-
-// The progressive accumulator at `elems` floats: reallocated when a frame of another size arrives (zero: a
-// render starts a new accumulation; cr_set_accumulator overwrites it anyway)
-static int size_accumulator(cr_ctx *c, size_t elems, bool zero) {
-    if (elems == c->accum_elems) return CR_OK;
-    if (c->d_accum) hipFree(c->d_accum);
-    c->d_accum = nullptr;
-    c->accum_elems = 0;
-    if (hipMalloc(&c->d_accum, elems * sizeof(float)) != hipSuccess) return fail(c, CR_E_OOM, "accumulator");
-    c->accum_elems = elems;
-    if (zero) HIPCHK(hipMemset(c->d_accum, 0, elems * sizeof(float)));
-    return CR_OK;
-}
-// ... and the moment accumulator beside it (cr_render_layers_noise, cr_render_until, cr_set_noise_accumulator)
-static int size_noise_accumulator(cr_ctx *c, size_t elems, bool zero) {
-    if (elems == c->accum2_elems) return CR_OK;
-    if (c->d_accum2) hipFree(c->d_accum2);
-    c->d_accum2 = nullptr;
-    c->accum2_elems = 0;
-    if (hipMalloc(&c->d_accum2, elems * sizeof(float)) != hipSuccess) return fail(c, CR_E_OOM, "moment accumulator");
-    c->accum2_elems = elems;
-    if (zero) HIPCHK(hipMemset(c->d_accum2, 0, elems * sizeof(float)));
-    return CR_OK;
-}
-
-int cr_render(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, float *accum_rgb_out) {
-    if (!c) return CR_E_INVALID;
-    if (c->device < 0) return fail(c, CR_E_HIP, c->err.empty() ? "no device" : c->err);
-    if (!accum_rgb_out || !p) return fail(c, CR_E_INVALID, "null output/params");
-    cr_render_params q = *p;
-    if (q.nranks == 0) q.nranks = 1;
-    int rc = check_params(c, &q);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(c->device));
-    const size_t elems = (size_t)q.xres * q.yres * 3;
-    if (int r = size_accumulator(c, elems, true)) return r;
-    rc = run_render(c, cam, &q, c->d_accum, cr::MODE_BLEND, c->stream);
-    if (rc) return rc;
-    HIPCHK(hipMemcpy(accum_rgb_out, c->d_accum, elems * sizeof(float), hipMemcpyDeviceToHost));
-    return CR_OK;
-}
-
 
 // cr_render over nlayers layers in pass groups: up to LAYER_GROUP layers per pass, the frame cut
 // into the fewest tile-split pieces whose paths fit one chunk (DistributedFrame.plan_layers)
@@ -724,11 +332,10 @@ static const uint32_t LAYER_GROUP = 32, MAX_PIECES = 64;
 // 987, nanobox stand-in 1922 -> 2173 Mray/s) and lose on a handful of triangles (cornell_box, 36:
 // 147.6 -> 153.8 ms per layer), whose queues gain no coherence from denser passes
 static const uint32_t PIECES_MIN_TRIS = 1024;
-uint32_t cr_scene_triangles(cr_ctx *c) { return c && c->has_scene ? c->n_tris : 0u; }
+
 // The largest nl <= want (>= 1) whose paths fit one chunk when p's share is cut into *m pieces (the
 // fewest; scenes of at least PIECES_MIN_TRIS triangles only): for the whole frame (nranks 1) the
 // ranks of an m-way split, for rank r of N the ranks r + kN of an N * m split
-} // extern "C"
 uint32_t crx::group_layers(cr_ctx *c, const cr_render_params *p, uint32_t want, uint32_t *m_out) {
     *m_out = 1;
     const uint32_t N = p->nranks ? p->nranks : 1;
@@ -758,7 +365,8 @@ static int render_layer_group(cr_ctx *c, const cr_camera *cam, const cr_render_p
         cr_render_params t = g;
         t.rank = k;
         t.nranks = m;
-        if (int rc = crx::run_render(c, cam, &t, c->d_accum, cr::MODE_BLEND, c->stream, nl, 0, 1, 0, m2)) return rc;
+        if (int rc = crx::run_render(c, cam, &t, c->d_accum.as<float>(), cr::MODE_BLEND, c->stream, nl, 0, 1, 0, m2))
+            return rc;
         sum.add(c);
     }
     *nl_out = nl;
@@ -774,48 +382,29 @@ static int render_layer_groups(cr_ctx *c, const cr_camera *cam, const cr_render_
     }
     return CR_OK;
 }
-extern "C" {
 
-uint32_t cr_layers_per_group(cr_ctx *c, const cr_render_params *p, uint32_t want) {
-    if (!c || c->device < 0 || !c->has_scene || !p || want < 1 || check_params(c, p) != CR_OK) return 1;
-    uint32_t m = 1;
-    return group_layers(c, p, want, &m);
-}
-
-int cr_render_layers(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, uint32_t nlayers,
-                     float *accum_rgb_out) {
-    if (!c) return CR_E_INVALID;
-    if (c->device < 0) return fail(c, CR_E_HIP, c->err.empty() ? "no device" : c->err);
-    if (!accum_rgb_out || !p || nlayers < 1) return fail(c, CR_E_INVALID, "null output/params or no layers");
+// cr_render_layers and (moments) cr_render_layers_noise behind their guards: layers p->layer .. + nlayers - 1 of the
+// whole frame in pass groups, into the ctx's accumulator(s) and out to the host
+static int render_whole_frame(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, uint32_t nlayers,
+                              const char *who, float *out, bool moments, float *m2_out) {
     cr_render_params q = *p;
     if (q.nranks == 0) q.nranks = 1;
-    if (q.nranks != 1) return fail(c, CR_E_INVALID, "cr_render_layers: the whole frame (nranks 1)");
-    int rc = check_params(c, &q);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(c->device));
+    if (q.nranks != 1) return fail(c, CR_E_INVALID, std::string(who) + ": the whole frame (nranks 1)");
+    if (int rc = check_params(c, &q)) return rc;
     const size_t elems = (size_t)q.xres * q.yres * 3;
-    if (int r = size_accumulator(c, elems, true)) return r;
+    if (int r = size_accumulator(c, c->d_accum, "accumulator", elems, true)) return r;
+    if (moments)
+        if (int r = size_accumulator(c, c->d_accum2, "moment accumulator", elems, true)) return r;
     PassTotals sum;
-    if ((rc = render_layer_groups(c, cam, q, nlayers, nullptr, sum))) return rc;
+    if (int rc = render_layer_groups(c, cam, q, nlayers, moments ? c->d_accum2.as<float>() : nullptr, sum)) return rc;
     sum.store(c);
-    HIPCHK(hipMemcpy(accum_rgb_out, c->d_accum, elems * sizeof(float), hipMemcpyDeviceToHost));
-    return CR_OK;
-}
-
-int cr_set_accumulator(cr_ctx *c, uint32_t xres, uint32_t yres, const float *rgb) {
-    if (!c) return CR_E_INVALID;
-    if (c->device < 0) return fail(c, CR_E_HIP, c->err.empty() ? "no device" : c->err);
-    if (!rgb || !xres || !yres) return fail(c, CR_E_INVALID, "null / empty accumulator");
-    HIPCHK(hipSetDevice(c->device));
-    const size_t elems = (size_t)xres * yres * 3;
-    if (int r = size_accumulator(c, elems, false)) return r;
-    HIPCHK(hipMemcpy(c->d_accum, rgb, elems * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(out, c->d_accum.ptr, elems * sizeof(float), hipMemcpyDeviceToHost));
+    if (m2_out) HIPCHK(hipMemcpy(m2_out, c->d_accum2.ptr, elems * sizeof(float), hipMemcpyDeviceToHost));
     return CR_OK;
 }
 
 // ---- noise estimate.  The new entry points check their arguments first, then the device,
 // then the scene: a null pointer is CR_E_INVALID with or without a GPU.
-} // extern "C"
 static int check_noise_params(cr_ctx *c, const cr_noise_params *np) {
     if (!np) return fail(c, CR_E_INVALID, "null noise params");
     if (!(np->floor > 0.f) || std::isinf(np->floor)) return fail(c, CR_E_INVALID, "noise floor must be > 0 and finite");
@@ -851,210 +440,20 @@ static int enqueue_noise(cr_ctx *c, uint32_t xres, uint32_t yres, uint32_t layer
 static int noise_of_accumulators(cr_ctx *c, uint32_t xres, uint32_t yres, uint32_t layers, uint32_t spp,
                                  const cr_noise_params *np, float *err_out, cr_noise_stats *stats_out) {
     const size_t npix = (size_t)xres * yres;
-    if (c->accum_elems != 3 * npix || c->accum2_elems != 3 * npix || !c->d_accum || !c->d_accum2)
+    if (c->d_accum.count<float>() != 3 * npix || c->d_accum2.count<float>() != 3 * npix || !c->d_accum.ptr ||
+        !c->d_accum2.ptr)
         return fail(c, CR_E_INVALID, "cr_noise: no frame and moment accumulator of this size (render with "
                                      "cr_render_layers_noise / cr_render_until first)");
-    if (int r = grow(c, &c->d_nstats, c->nstats_bytes, sizeof(cr_noise_stats))) return r;
+    if (int r = grow(c, c->d_nstats, sizeof(cr_noise_stats))) return r;
     if (err_out)
-        if (int r = grow(c, &c->d_err, c->err_bytes, npix * sizeof(float))) return r;
-    if (int r = enqueue_noise(c, xres, yres, layers, spp, np, c->d_accum, c->d_accum2,
-                              err_out ? (float *)c->d_err : nullptr, (cr_noise_stats *)c->d_nstats, c->stream))
+        if (int r = grow(c, c->d_err, npix * sizeof(float))) return r;
+    if (int r = enqueue_noise(c, xres, yres, layers, spp, np, c->d_accum.as<float>(), c->d_accum2.as<float>(),
+                              err_out ? c->d_err.as<float>() : nullptr, c->d_nstats.as<cr_noise_stats>(), c->stream))
         return r;
-    HIPCHK(hipMemcpyAsync(stats_out, c->d_nstats, sizeof(cr_noise_stats), hipMemcpyDeviceToHost, c->stream));
-    if (err_out) HIPCHK(hipMemcpyAsync(err_out, c->d_err, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(stats_out, c->d_nstats.ptr, sizeof(cr_noise_stats), hipMemcpyDeviceToHost, c->stream));
+    if (err_out)
+        HIPCHK(hipMemcpyAsync(err_out, c->d_err.ptr, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    return CR_OK;
-}
-extern "C" {
-
-void cr_noise_struct_sizes(uint32_t *params_bytes, uint32_t *stats_bytes) {
-    if (params_bytes) *params_bytes = (uint32_t)sizeof(cr_noise_params);
-    if (stats_bytes) *stats_bytes = (uint32_t)sizeof(cr_noise_stats);
-}
-
-int cr_render_layers_noise_device(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, uint32_t nlayers,
-                                  float *d_frame, float *d_m2, void *stream) {
-    if (!c) return CR_E_INVALID;
-    if (!cam || !p || !d_frame || !d_m2 || nlayers < 1)
-        return fail(c, CR_E_INVALID, "null camera/params/frame/moment frame or no layers");
-    if (c->device < 0) return fail(c, CR_E_HIP, c->err.empty() ? "no device" : c->err);
-    return run_render(c, cam, p, d_frame, cr::MODE_BLEND, (hipStream_t)stream, nlayers, 0, 1, 0, d_m2);
-}
-
-int cr_noise_device(cr_ctx *c, uint32_t xres, uint32_t yres, uint32_t layers, uint32_t spp, const cr_noise_params *np,
-                    const float *d_frame, const float *d_m2, float *d_err, cr_noise_stats *d_stats, void *stream) {
-    if (!c) return CR_E_INVALID;
-    if (!d_frame || !d_m2 || !d_stats) return fail(c, CR_E_INVALID, "null frame / moment frame / stats");
-    if (int r = check_noise_params(c, np)) return r;
-    if (int r = check_noise_shape(c, xres, yres, layers, spp)) return r;
-    if (c->device < 0) return fail(c, CR_E_HIP, c->err.empty() ? "no device" : c->err);
-    return enqueue_noise(c, xres, yres, layers, spp, np, d_frame, d_m2, d_err, d_stats, (hipStream_t)stream);
-}
-
-int cr_render_layers_noise(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, uint32_t nlayers,
-                           float *accum_rgb_out, float *m2_out) {
-    if (!c) return CR_E_INVALID;
-    if (!cam || !p || !accum_rgb_out || nlayers < 1)
-        return fail(c, CR_E_INVALID, "null camera/params/output or no layers");
-    if (c->device < 0) return fail(c, CR_E_HIP, c->err.empty() ? "no device" : c->err);
-    cr_render_params q = *p;
-    if (q.nranks == 0) q.nranks = 1;
-    if (q.nranks != 1) return fail(c, CR_E_INVALID, "cr_render_layers_noise: the whole frame (nranks 1)");
-    int rc = check_params(c, &q);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(c->device));
-    const size_t elems = (size_t)q.xres * q.yres * 3;
-    if (int r = size_accumulator(c, elems, true)) return r;
-    if (int r = size_noise_accumulator(c, elems, true)) return r;
-    PassTotals sum;
-    if ((rc = render_layer_groups(c, cam, q, nlayers, c->d_accum2, sum))) return rc;
-    sum.store(c);
-    HIPCHK(hipMemcpy(accum_rgb_out, c->d_accum, elems * sizeof(float), hipMemcpyDeviceToHost));
-    if (m2_out) HIPCHK(hipMemcpy(m2_out, c->d_accum2, elems * sizeof(float), hipMemcpyDeviceToHost));
-    return CR_OK;
-}
-
-int cr_noise(cr_ctx *c, uint32_t xres, uint32_t yres, uint32_t layers, uint32_t spp, const cr_noise_params *np,
-             float *err_out, cr_noise_stats *stats_out) {
-    if (!c) return CR_E_INVALID;
-    if (!stats_out) return fail(c, CR_E_INVALID, "null stats");
-    if (int r = check_noise_params(c, np)) return r;
-    if (int r = check_noise_shape(c, xres, yres, layers, spp)) return r;
-    if (c->device < 0) return fail(c, CR_E_HIP, c->err.empty() ? "no device" : c->err);
-    return noise_of_accumulators(c, xres, yres, layers, spp, np, err_out, stats_out);
-}
-
-int cr_set_noise_accumulator(cr_ctx *c, uint32_t xres, uint32_t yres, const float *m2) {
-    if (!c) return CR_E_INVALID;
-    if (!m2 || !xres || !yres) return fail(c, CR_E_INVALID, "null / empty moment accumulator");
-    if (c->device < 0) return fail(c, CR_E_HIP, c->err.empty() ? "no device" : c->err);
-    HIPCHK(hipSetDevice(c->device));
-    const size_t elems = (size_t)xres * yres * 3;
-    if (int r = size_noise_accumulator(c, elems, false)) return r;
-    HIPCHK(hipMemcpy(c->d_accum2, m2, elems * sizeof(float), hipMemcpyHostToDevice));
-    return CR_OK;
-}
-
-int cr_render_until(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, uint32_t min_layers,
-                    uint32_t max_layers, uint32_t check_every, const cr_noise_params *np, uint64_t max_above,
-                    float *accum_rgb_out, cr_noise_stats *stats_out) {
-    if (!c) return CR_E_INVALID;
-    if (!cam || !p || !accum_rgb_out || !stats_out) return fail(c, CR_E_INVALID, "null camera/params/output/stats");
-    if (int r = check_noise_params(c, np)) return r;
-    if (check_every < 1 || p->layer < 1 || max_layers < p->layer)
-        return fail(c, CR_E_INVALID, "cr_render_until: check_every >= 1 and 1 <= p->layer <= max_layers");
-    if (c->device < 0) return fail(c, CR_E_HIP, c->err.empty() ? "no device" : c->err);
-    cr_render_params q = *p;
-    if (q.nranks == 0) q.nranks = 1;
-    if (q.nranks != 1) return fail(c, CR_E_INVALID, "cr_render_until: the whole frame (nranks 1)");
-    int rc = check_params(c, &q);
-    if (rc) return rc;
-    if ((rc = check_noise_shape(c, q.xres, q.yres, max_layers, q.spp))) return rc;
-    HIPCHK(hipSetDevice(c->device));
-    const size_t elems = (size_t)q.xres * q.yres * 3;
-    if (int r = size_accumulator(c, elems, true)) return r;
-    if (int r = size_noise_accumulator(c, elems, true)) return r;
-    PassTotals sum;
-    cr_noise_stats st{};
-    // one pass group of at most check_every layers (fewer when fewer fit a group), then a check
-    for (uint32_t layer = q.layer - 1; layer < max_layers;) {
-        uint32_t n = 0;
-        cr_render_params g = q;
-        g.layer = layer + 1;
-        if ((rc = render_layer_group(c, cam, g, std::min(check_every, max_layers - layer), c->d_accum2, sum, &n)))
-            return rc;
-        layer += n;
-        if ((rc = noise_of_accumulators(c, q.xres, q.yres, layer, q.spp, np, nullptr, &st))) return rc;
-        if (layer >= min_layers && st.above <= max_above) break;
-    }
-    sum.store(c);
-    HIPCHK(hipMemcpy(accum_rgb_out, c->d_accum, elems * sizeof(float), hipMemcpyDeviceToHost));
-    *stats_out = st;
-    return CR_OK;
-}
-
-int cr_render_device(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, float *d_frame, void *stream) {
-    if (!c) return CR_E_INVALID;
-    if (c->device < 0) return fail(c, CR_E_HIP, c->err.empty() ? "no device" : c->err);
-    return run_render(c, cam, p, d_frame, cr::MODE_BLEND, (hipStream_t)stream);
-}
-
-int cr_render_tiles_device(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, float *d_tiles,
-                           void *stream) {
-    if (!c) return CR_E_INVALID;
-    if (c->device < 0) return fail(c, CR_E_HIP, c->err.empty() ? "no device" : c->err);
-    return run_render(c, cam, p, d_tiles, cr::MODE_TILES, (hipStream_t)stream);
-}
-
-uint32_t cr_layers_per_pass(cr_ctx *c, const cr_render_params *p, uint32_t want) {
-    if (!c || c->device < 0 || !c->has_scene || !p || want < 1 || check_params(c, p) != CR_OK) return 1;
-    if (c->kernel != 2 || c->wf_lanes != 1 || c->full_counters) return 1;
-    if (hipSetDevice(c->device) != hipSuccess) return 1;
-    const uint64_t items = (uint64_t)cr_tiles_for_rank(p, p->rank) * tile_of(p) * tile_of(p);
-    const uint64_t paths_cap = std::min<uint64_t>(c->wf_paths, wf_path_cap(c, p->k));
-    uint32_t nl = want;
-    while (nl > 1 && !cr::wf_layers_fit(items, p->spp, nl, paths_cap, c->sample_buf)) nl--;
-    return nl;
-}
-
-int cr_render_layers_device(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, uint32_t nlayers,
-                            float *d_frame, void *stream) {
-    if (!c) return CR_E_INVALID;
-    if (c->device < 0) return fail(c, CR_E_HIP, c->err.empty() ? "no device" : c->err);
-    return run_render(c, cam, p, d_frame, cr::MODE_BLEND, (hipStream_t)stream, nlayers);
-}
-
-int cr_render_tiles_layers_device(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, uint32_t nlayers,
-                                  float *d_tiles, void *stream) {
-    if (!c) return CR_E_INVALID;
-    if (c->device < 0) return fail(c, CR_E_HIP, c->err.empty() ? "no device" : c->err);
-    if (!p || p->nranks <= 1 || nlayers <= 1 || cr_layers_per_pass(c, p, nlayers) == nlayers)
-        return run_render(c, cam, p, d_tiles, cr::MODE_TILES, (hipStream_t)stream, nlayers);
-    // the rank's tiles in pieces (ranks r + kN of an N * m split: every tile slot keeps its pixels
-    // for any split of more than one rank), each written into the rank's compact buffer
-    uint32_t m = 1;
-    if (group_layers(c, p, nlayers, &m) != nlayers)
-        return fail(c, CR_E_INVALID, "layers per pass: the rank's share does not fit in pieces");
-    const uint64_t stride = (uint64_t)cr_tiles_for_rank(p, 0) * tile_of(p) * tile_of(p) * 3;
-    PassTotals sum;
-    for (uint32_t k = 0; k < m; k++) {
-        cr_render_params t = *p;
-        t.rank = p->rank + k * p->nranks;
-        t.nranks = p->nranks * m;
-        if (cr_tiles_for_rank(&t, t.rank) == 0) continue;
-        if (int rc = run_render(c, cam, &t, d_tiles, cr::MODE_TILES, (hipStream_t)stream, nlayers, k, m, stride))
-            return rc;
-        sum.add(c);
-    }
-    sum.store(c);
-    return CR_OK;
-}
-
-int cr_blend_tiles_device(cr_ctx *c, const cr_render_params *p, const float *d_gathered, float *d_frame,
-                          void *stream) {
-    return cr_blend_tiles_layers_device(c, p, 1, d_gathered, d_frame, stream);
-}
-
-int cr_blend_tiles_layers_device(cr_ctx *c, const cr_render_params *p, uint32_t nlayers, const float *d_gathered,
-                                 float *d_frame, void *stream) {
-    if (!c) return CR_E_INVALID;
-    if (c->device < 0) return fail(c, CR_E_HIP, c->err.empty() ? "no device" : c->err);
-    if (!p || !d_gathered || !d_frame || p->nranks < 1 || p->layer < 1 || nlayers < 1)
-        return fail(c, CR_E_INVALID, "bad blend args");
-    HIPCHK(hipSetDevice(c->device));
-    cr::BlendArgs B{};
-    B.gathered = d_gathered;
-    B.frame = d_frame;
-    B.xres = p->xres;
-    B.yres = p->yres;
-    B.tile = tile_of(p);
-    B.tiles_x = (p->xres + B.tile - 1) / B.tile;
-    B.nranks = p->nranks;
-    B.max_tiles = cr_tiles_for_rank(p, 0);
-    B.layer = p->layer;
-    B.nl = nlayers;
-    int e = cr::launch_blend(B, (hipStream_t)stream);
-    if (e) return hip_fail(c, (hipError_t)e, "blend kernel launch");
     return CR_OK;
 }
 
@@ -1074,62 +473,18 @@ static float tm_find_knee_f(float x, float y) {
     return (f0 + f1) / 2;
 }
 
-void cr_tonemap_setup(float exposure, float defog, float kneeLow, float kneeHigh, float gamma, cr_tonemap_params *t) {
-    if (!t) return;
-    t->m = powf(2.f, exposure + 2.47393f);
-    t->s = 255.f * powf(2.f, -3.5f * gamma);
-    t->kl = powf(2.f, kneeLow);
-    t->f = tm_find_knee_f(powf(2.f, kneeHigh), powf(2.f, 3.5) - t->kl);
-    t->defog = defog;
-    t->gamma = gamma;
-}
-
-int cr_tonemap_device(cr_ctx *c, const cr_tonemap_params *t, uint32_t xres, uint32_t yres, const float *d_rgb,
-                      uint8_t *d_bytes, void *stream) {
-    if (!c) return CR_E_INVALID;
-    if (c->device < 0) return fail(c, CR_E_HIP, c->err.empty() ? "no device" : c->err);
-    if (!t || !d_rgb || !d_bytes) return fail(c, CR_E_INVALID, "bad tonemap args");
-    if ((uint64_t)xres * yres > (1ull << 31)) return fail(c, CR_E_INVALID, "image too large");
-    HIPCHK(hipSetDevice(c->device));
-    const cr::TonemapArgs T{d_rgb, d_bytes, xres, yres, t->m, t->s, t->kl, t->f, t->defog, t->gamma};
-    const int e = cr::launch_tonemap(T, (hipStream_t)stream);
-    if (e) return hip_fail(c, (hipError_t)e, "tonemap kernel launch");
-    return CR_OK;
-}
-
-int cr_tonemap(cr_ctx *c, const cr_tonemap_params *t, uint32_t xres, uint32_t yres, uint8_t *bytes_out) {
-    if (!c) return CR_E_INVALID;
-    if (c->device < 0) return fail(c, CR_E_HIP, c->err.empty() ? "no device" : c->err);
-    if (!bytes_out) return fail(c, CR_E_INVALID, "null output");
-    const size_t n = (size_t)3 * xres * yres;
-    if (!c->d_accum || c->accum_elems != n) return fail(c, CR_E_INVALID, "no rendered frame of this size");
-    HIPCHK(hipSetDevice(c->device));
-    void *d_bytes = nullptr;
-    if (hipMalloc(&d_bytes, n ? n : 1) != hipSuccess) return fail(c, CR_E_OOM, "tonemap buffer");
-    int rc = cr_tonemap_device(c, t, xres, yres, c->d_accum, (uint8_t *)d_bytes, c->stream);
-    if (rc == CR_OK) {
-        const hipError_t e = hipMemcpyAsync(bytes_out, d_bytes, n, hipMemcpyDeviceToHost, c->stream);
-        const hipError_t e2 = e == hipSuccess ? hipStreamSynchronize(c->stream) : e;
-        if (e2 != hipSuccess) rc = hip_fail(c, e2, "tonemap copy");
-    }
-    hipFree(d_bytes);
-    return rc;
-}
-
 static int run_query(cr_ctx *c, uint32_t n, bool shadow, const float *orig, const float *dir, const float *dist,
                      const uint32_t *light, uint32_t *hit, uint32_t *tri, float *bary, float *dist_out) {
-    if (!c) return CR_E_INVALID;
-    if (c->device < 0) return fail(c, CR_E_HIP, c->err.empty() ? "no device" : c->err);
+    if (int rc = enter(c)) return rc;
     if (!c->has_scene) return fail(c, CR_E_NOSCENE, "no scene uploaded");
     if (n == 0) return CR_OK;
     if (!orig || !dir || !hit) return fail(c, CR_E_INVALID, "null query arrays");
     if (shadow && (!dist || !light)) return fail(c, CR_E_INVALID, "null shadow distance / light arrays");
-    HIPCHK(hipSetDevice(c->device));
-    char *buf = nullptr;
+    DevBuf buf;
     const size_t fbytes = (size_t)n * 3 * sizeof(float);
     const size_t total = 2 * fbytes + 4 * (size_t)n * sizeof(uint32_t) + 3 * (size_t)n * sizeof(float) + 256;
-    if (hipMalloc(&buf, total) != hipSuccess) return fail(c, CR_E_OOM, "query buffers");
-    char *p = buf;
+    if (int r = grow(c, buf, total, "query buffers")) return r;
+    char *p = buf.as<char>();
     auto take = [&](size_t b) { char *r = p; p += (b + 15) & ~(size_t)15; return r; };
     cr::QueryArgs Q{};
     Q.S = c->S;
@@ -1146,10 +501,10 @@ static int run_query(cr_ctx *c, uint32_t n, bool shadow, const float *orig, cons
     if (e == hipSuccess) e = hipMemcpy(d_dir, dir, fbytes, hipMemcpyHostToDevice);
     if (e == hipSuccess && shadow) e = hipMemcpy(d_dist, dist, n * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess && shadow) e = hipMemcpy(d_light, light, n * sizeof(uint32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(c->d_counters, 0, cr::CTR_SLOTS * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemset(c->d_counters.ptr, 0, cr::CTR_SLOTS * sizeof(unsigned long long));
     Q.orig = d_orig; Q.dir = d_dir; Q.dist = d_dist; Q.light = d_light;
     Q.hit = d_hit; Q.tri = d_tri; Q.bary = d_bary; Q.dist_out = d_do;
-    Q.counters = c->d_counters;
+    Q.counters = c->d_counters.as<unsigned long long>();
     if (e == hipSuccess) e = (hipError_t)cr::launch_intersect(Q, nullptr);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(hit, d_hit, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
@@ -1157,22 +512,10 @@ static int run_query(cr_ctx *c, uint32_t n, bool shadow, const float *orig, cons
     if (e == hipSuccess && !shadow && bary) e = hipMemcpy(bary, d_bary, 2 * n * sizeof(float), hipMemcpyDeviceToHost);
     if (e == hipSuccess && !shadow && dist_out) e = hipMemcpy(dist_out, d_do, n * sizeof(float), hipMemcpyDeviceToHost);
     unsigned long long h[cr::CTR_SLOTS] = {};
-    if (e == hipSuccess) e = hipMemcpy(h, c->d_counters, sizeof(h), hipMemcpyDeviceToHost);
-    hipFree(buf);
+    if (e == hipSuccess) e = hipMemcpy(h, c->d_counters.ptr, sizeof(h), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return hip_fail(c, e, "intersect");
     c->last = counters_of(h);
     return CR_OK;
-}
-
-int cr_intersect(cr_ctx *c, uint32_t n, const float *orig, const float *dir, uint32_t *hit, uint32_t *tri,
-                 float *bary, float *dist) {
-    return run_query(c, n, false, orig, dir, nullptr, nullptr, hit, tri, bary, dist);
-}
-
-int cr_intersect_shadow(cr_ctx *c, uint32_t n, const float *orig, const float *dir, const float *dist,
-                        const uint32_t *light_tri, uint32_t *occluded) {
-    if (c && n && (!dist || !light_tri)) return fail(c, CR_E_INVALID, "null dist/light");
-    return run_query(c, n, true, orig, dir, dist, light_tri, occluded, nullptr, nullptr, nullptr);
 }
 
 // ---- device-resident queries ----
@@ -1223,21 +566,19 @@ size_t carve_query(const cr_ctx *c, uint32_t cap, bool trace, int variant, char 
 
 int run_query_device(cr_ctx *c, uint32_t n, bool shadow, const float *orig, const float *dir, const float *dist,
                      const uint32_t *light, uint32_t *hit, uint32_t *tri, float *bary, float *dist_out, void *stream) {
-    if (!c) return CR_E_INVALID;
-    if (c->device < 0) return fail(c, CR_E_HIP, c->err.empty() ? "no device" : c->err);
+    if (int rc = enter(c)) return rc;
     if (!c->has_scene) return fail(c, CR_E_NOSCENE, "no scene uploaded");
     if (n == 0) return CR_OK;
     if (n == 0xffffffffu) return fail(c, CR_E_INVALID, "at most 2^32 - 2 queries per call");
     if (!orig || !dir || !hit) return fail(c, CR_E_INVALID, "null query arrays");
     if (shadow && (!dist || !light)) return fail(c, CR_E_INVALID, "null shadow distance / light arrays");
-    HIPCHK(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
     const int variant = default_trace_build(c); // (the option "variant" is the render's)
     const bool cull = cr::wf_variant_leaf_cull(variant);
     const bool trace = c->query_route != 1 && n >= c->query_trace_min;
     const uint32_t chunk = std::min(n, c->query_chunk);
     QueryBufs B;
-    if (!c->d_query || (trace && (!c->q_trace || c->q_cap < chunk || c->q_depth != c->stack_depth))) {
+    if (!c->d_query.ptr || (trace && (!c->q_trace || c->q_cap < chunk || c->q_depth != c->stack_depth))) {
         // regrow: the old buffers may still be in use by the last call
         if (c->q_pending) HIPCHK(hipEventSynchronize(c->q_ev));
         c->q_pending = false;
@@ -1246,22 +587,20 @@ int run_query_device(cr_ctx *c, uint32_t n, bool shadow, const float *orig, cons
         const size_t need = carve_query(c, cap, tr, variant, nullptr, B);
         if (tr && cr::gstack_bytes(c->stack_depth, B.gstride) >= (1ull << 32)) // (gstack_at's 32-bit offsets)
             return fail(c, CR_E_INVALID, "stack overflow area too large");
-        if (c->d_query) hipFree(c->d_query);
-        c->d_query = nullptr;
-        c->query_bytes = 0;
+        c->d_query.release();
         c->q_cap = 0;
         c->q_trace = false;
-        if (hipMalloc(&c->d_query, need) != hipSuccess) return fail(c, CR_E_OOM, "query buffers");
-        c->query_bytes = need;
+        if (hipMalloc(&c->d_query.ptr, need) != hipSuccess) return fail(c, CR_E_OOM, "query buffers");
+        c->d_query.cap = need;
         c->q_cap = cap;
         c->q_trace = tr;
         c->q_depth = c->stack_depth;
-        carve_query(c, cap, tr, variant, (char *)c->d_query, B);
+        carve_query(c, cap, tr, variant, c->d_query.as<char>(), B);
         HIPCHK(hipMemsetAsync(B.counters, 0, cr::CTR_SLOTS * sizeof(unsigned long long), st));
     } else if (c->q_pending && st != c->q_stream) {
         HIPCHK(hipStreamWaitEvent(st, c->q_ev, 0));
     }
-    carve_query(c, c->q_cap, c->q_trace, variant, (char *)c->d_query, B);
+    carve_query(c, c->q_cap, c->q_trace, variant, c->d_query.as<char>(), B);
 
     cr::RenderArgs A{};
     cr::WfArgs W{};
@@ -1346,6 +685,346 @@ int run_query_device(cr_ctx *c, uint32_t n, bool shadow, const float *orig, cons
 }
 } // namespace
 
+extern "C" {
+
+cr_ctx *cr_create(int device) {
+    cr_ctx *c = new cr_ctx();
+    int n = 0;
+    auto none = [c](const char *why) { return c->err = why, c->device = -1, c; }; // (surfaced on first use)
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return none("no HIP device");
+    if (device < 0 || device >= n) return none("bad device index");
+    if (hipSetDevice(device) != hipSuccess) return none("hipSetDevice failed");
+    c->device = device;
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->num_cus = prop.multiProcessorCount;
+    if (c->stream.create() != hipSuccess || c->side.create() != hipSuccess ||
+        c->fork.create(false) != hipSuccess || c->join.create(false) != hipSuccess ||
+        c->stream2.create() != hipSuccess || c->side2.create() != hipSuccess ||
+        c->fork2.create(false) != hipSuccess || c->join2.create(false) != hipSuccess ||
+        c->lane_ev[0].create(false) != hipSuccess || c->lane_ev[1].create(false) != hipSuccess ||
+        c->hcnt.create(4) != hipSuccess || c->ev0.create(true) != hipSuccess || c->ev1.create(true) != hipSuccess ||
+        c->q_ev.create(false) != hipSuccess ||
+        c->d_counters.grow(cr::CTR_SLOTS * sizeof(unsigned long long)) != CR_OK) {
+        delete c; // all or nothing: what was created goes now, while its device is current
+        return (c = new cr_ctx())->err = "device init failed", c;
+    }
+    return c;
+}
+
+void cr_destroy(cr_ctx *c) {
+    if (!c) return;
+    if (c->device >= 0) {
+        hipSetDevice(c->device);
+        release_dist(c); // the communicator before its tile, gather and flag buffers
+        if (c->q_pending) hipEventSynchronize(c->q_ev); // a pending query still uses d_query
+    }
+    delete c; // (a ctx without a device holds no handle: cr_create)
+}
+
+const char *cr_last_error(cr_ctx *c) { return c ? c->err.c_str() : "null context"; }
+
+int cr_upload_scene(cr_ctx *c, const cr_scene_desc *d) {
+    if (int rc = enter(c)) return rc;
+    if (!d || !d->nodes || d->n_nodes == 0) return fail(c, CR_E_INVALID, "empty kd tree");
+    if (d->n_tris && (!d->tri_pos || !d->tri_normal || !d->tri_kd || !d->tri_ke || !d->tri_uv))
+        return fail(c, CR_E_INVALID, "missing triangle arrays");
+    if (d->max_depth > 256) return fail(c, CR_E_DEPTH, "kd tree deeper than 256");
+    free_scene(c);
+    // a new scene re-queries the path budget at its first plan (wf_path_cap): buffers grown since the last
+    // query (gather and tile buffers, the caller's own tensors) must not leave the chunk cap above the HBM
+    // that is free now.  Ranks still agree on a group's plan: plan_layers' all-reduce MIN, and the per-group
+    // agreement of cr_render_dist_layers_device / cr_group_render_layers
+    c->wf_mem_budget = 0;
+    // everything the kernels read, laid out on the host (scenelayout.hpp), then uploaded
+    cr::SceneLayout L;
+    std::string err;
+    if (int rc = cr::scene_layout(d, c->node_bfs, L, err)) return fail(c, rc, err);
+    c->S = L.S;
+    const uint32_t *levels_dev = nullptr;
+    int rc;
+    auto up = [&](const auto &h, auto **out) { return rc = upload(c, h, out); };
+    if (up(L.levels, &levels_dev) || up(L.nodes, &c->S.nodes) || up(L.fat, &c->S.fat) || up(L.recs, &c->S.recs) ||
+        up(L.lcullp, &c->S.lcullp) || up(L.lcullc, &c->S.lcullc) || up(L.tri, &c->S.tri) ||
+        up(L.mat_n, &c->S.mat_n) || up(L.mat_kd, &c->S.mat_kd) || up(L.mat_ke, &c->S.mat_ke) ||
+        up(L.mat_uv, &c->S.mat_uv) || up(L.lights, &c->S.lights) || up(L.texs, &c->S.texs) ||
+        up(L.texels, &c->S.texels)) {
+        free_scene(c);
+        return rc;
+    }
+    c->stack_depth = L.stack_depth;
+    c->n_refs = L.n_refs;
+    c->n_tris = L.n_tris;
+    for (int a = 0; a < 3; a++) c->splits[a] = std::move(L.splits[a]);
+    c->d_levels = levels_dev;
+    c->levels = std::move(L.level_off);
+    c->has_scene = true;
+    return CR_OK;
+}
+
+int cr_tile_origin(const cr_render_params *p, uint32_t rank, uint32_t local, uint32_t *x0, uint32_t *y0) {
+    if (!p || !x0 || !y0 || local >= cr_tiles_for_rank(p, rank)) return CR_E_INVALID;
+    const uint32_t T = tile_of(p), tx = (p->xres + T - 1) / T, s = rank + local * p->nranks;
+    *x0 = cr::tile_slot_column(s, tx, p->nranks) * T;
+    *y0 = s / tx * T;
+    return CR_OK;
+}
+
+uint32_t cr_tiles_for_rank(const cr_render_params *p, uint32_t rank) {
+    if (!p || p->nranks == 0 || rank >= p->nranks || p->xres == 0 || p->yres == 0) return 0;
+    const uint32_t T = tile_of(p);
+    const uint32_t nt = ((p->xres + T - 1) / T) * ((p->yres + T - 1) / T);
+    return nt > rank ? (nt - rank + p->nranks - 1) / p->nranks : 0;
+}
+
+int cr_render(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, float *accum_rgb_out) {
+    if (int rc = enter(c)) return rc;
+    if (!accum_rgb_out || !p) return fail(c, CR_E_INVALID, "null output/params");
+    cr_render_params q = *p;
+    if (q.nranks == 0) q.nranks = 1;
+    int rc = check_params(c, &q);
+    if (rc) return rc;
+    const size_t elems = (size_t)q.xres * q.yres * 3;
+    if (int r = size_accumulator(c, c->d_accum, "accumulator", elems, true)) return r;
+    rc = run_render(c, cam, &q, c->d_accum.as<float>(), cr::MODE_BLEND, c->stream);
+    if (rc) return rc;
+    HIPCHK(hipMemcpy(accum_rgb_out, c->d_accum.ptr, elems * sizeof(float), hipMemcpyDeviceToHost));
+    return CR_OK;
+}
+
+uint32_t cr_scene_triangles(cr_ctx *c) { return c && c->has_scene ? c->n_tris : 0u; }
+
+uint32_t cr_layers_per_group(cr_ctx *c, const cr_render_params *p, uint32_t want) {
+    if (!c || c->device < 0 || !c->has_scene || !p || want < 1 || check_params(c, p) != CR_OK) return 1;
+    uint32_t m = 1;
+    return group_layers(c, p, want, &m);
+}
+
+int cr_render_layers(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, uint32_t nlayers,
+                     float *accum_rgb_out) {
+    if (int rc = enter(c)) return rc;
+    if (!accum_rgb_out || !p || nlayers < 1) return fail(c, CR_E_INVALID, "null output/params or no layers");
+    return render_whole_frame(c, cam, p, nlayers, "cr_render_layers", accum_rgb_out, false, nullptr);
+}
+
+int cr_set_accumulator(cr_ctx *c, uint32_t xres, uint32_t yres, const float *rgb) {
+    if (int rc = enter(c)) return rc;
+    if (!rgb || !xres || !yres) return fail(c, CR_E_INVALID, "null / empty accumulator");
+    const size_t elems = (size_t)xres * yres * 3;
+    if (int r = size_accumulator(c, c->d_accum, "accumulator", elems, false)) return r;
+    HIPCHK(hipMemcpy(c->d_accum.ptr, rgb, elems * sizeof(float), hipMemcpyHostToDevice));
+    return CR_OK;
+}
+
+void cr_noise_struct_sizes(uint32_t *params_bytes, uint32_t *stats_bytes) {
+    if (params_bytes) *params_bytes = (uint32_t)sizeof(cr_noise_params);
+    if (stats_bytes) *stats_bytes = (uint32_t)sizeof(cr_noise_stats);
+}
+
+int cr_render_layers_noise_device(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, uint32_t nlayers,
+                                  float *d_frame, float *d_m2, void *stream) {
+    if (!c) return CR_E_INVALID;
+    if (!cam || !p || !d_frame || !d_m2 || nlayers < 1)
+        return fail(c, CR_E_INVALID, "null camera/params/frame/moment frame or no layers");
+    if (int rc = enter(c, false)) return rc;
+    return run_render(c, cam, p, d_frame, cr::MODE_BLEND, (hipStream_t)stream, nlayers, 0, 1, 0, d_m2);
+}
+
+int cr_noise_device(cr_ctx *c, uint32_t xres, uint32_t yres, uint32_t layers, uint32_t spp, const cr_noise_params *np,
+                    const float *d_frame, const float *d_m2, float *d_err, cr_noise_stats *d_stats, void *stream) {
+    if (!c) return CR_E_INVALID;
+    if (!d_frame || !d_m2 || !d_stats) return fail(c, CR_E_INVALID, "null frame / moment frame / stats");
+    if (int r = check_noise_params(c, np)) return r;
+    if (int r = check_noise_shape(c, xres, yres, layers, spp)) return r;
+    if (int rc = enter(c, false)) return rc;
+    return enqueue_noise(c, xres, yres, layers, spp, np, d_frame, d_m2, d_err, d_stats, (hipStream_t)stream);
+}
+
+int cr_render_layers_noise(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, uint32_t nlayers,
+                           float *accum_rgb_out, float *m2_out) {
+    if (!c) return CR_E_INVALID;
+    if (!cam || !p || !accum_rgb_out || nlayers < 1)
+        return fail(c, CR_E_INVALID, "null camera/params/output or no layers");
+    if (int rc = enter(c)) return rc;
+    return render_whole_frame(c, cam, p, nlayers, "cr_render_layers_noise", accum_rgb_out, true, m2_out);
+}
+
+int cr_noise(cr_ctx *c, uint32_t xres, uint32_t yres, uint32_t layers, uint32_t spp, const cr_noise_params *np,
+             float *err_out, cr_noise_stats *stats_out) {
+    if (!c) return CR_E_INVALID;
+    if (!stats_out) return fail(c, CR_E_INVALID, "null stats");
+    if (int r = check_noise_params(c, np)) return r;
+    if (int r = check_noise_shape(c, xres, yres, layers, spp)) return r;
+    if (int rc = enter(c, false)) return rc;
+    return noise_of_accumulators(c, xres, yres, layers, spp, np, err_out, stats_out);
+}
+
+int cr_set_noise_accumulator(cr_ctx *c, uint32_t xres, uint32_t yres, const float *m2) {
+    if (!c) return CR_E_INVALID;
+    if (!m2 || !xres || !yres) return fail(c, CR_E_INVALID, "null / empty moment accumulator");
+    if (int rc = enter(c)) return rc;
+    const size_t elems = (size_t)xres * yres * 3;
+    if (int r = size_accumulator(c, c->d_accum2, "moment accumulator", elems, false)) return r;
+    HIPCHK(hipMemcpy(c->d_accum2.ptr, m2, elems * sizeof(float), hipMemcpyHostToDevice));
+    return CR_OK;
+}
+
+int cr_render_until(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, uint32_t min_layers,
+                    uint32_t max_layers, uint32_t check_every, const cr_noise_params *np, uint64_t max_above,
+                    float *accum_rgb_out, cr_noise_stats *stats_out) {
+    if (!c) return CR_E_INVALID;
+    if (!cam || !p || !accum_rgb_out || !stats_out) return fail(c, CR_E_INVALID, "null camera/params/output/stats");
+    if (int r = check_noise_params(c, np)) return r;
+    if (check_every < 1 || p->layer < 1 || max_layers < p->layer)
+        return fail(c, CR_E_INVALID, "cr_render_until: check_every >= 1 and 1 <= p->layer <= max_layers");
+    if (int rc = enter(c)) return rc;
+    cr_render_params q = *p;
+    if (q.nranks == 0) q.nranks = 1;
+    if (q.nranks != 1) return fail(c, CR_E_INVALID, "cr_render_until: the whole frame (nranks 1)");
+    int rc = check_params(c, &q);
+    if (rc) return rc;
+    if ((rc = check_noise_shape(c, q.xres, q.yres, max_layers, q.spp))) return rc;
+    const size_t elems = (size_t)q.xres * q.yres * 3;
+    if (int r = size_accumulator(c, c->d_accum, "accumulator", elems, true)) return r;
+    if (int r = size_accumulator(c, c->d_accum2, "moment accumulator", elems, true)) return r;
+    PassTotals sum;
+    cr_noise_stats st{};
+    // one pass group of at most check_every layers (fewer when fewer fit a group), then a check
+    for (uint32_t layer = q.layer - 1; layer < max_layers;) {
+        uint32_t n = 0;
+        cr_render_params g = q;
+        g.layer = layer + 1;
+        if ((rc = render_layer_group(c, cam, g, std::min(check_every, max_layers - layer), c->d_accum2.as<float>(), sum,
+                                     &n)))
+            return rc;
+        layer += n;
+        if ((rc = noise_of_accumulators(c, q.xres, q.yres, layer, q.spp, np, nullptr, &st))) return rc;
+        if (layer >= min_layers && st.above <= max_above) break;
+    }
+    sum.store(c);
+    HIPCHK(hipMemcpy(accum_rgb_out, c->d_accum.ptr, elems * sizeof(float), hipMemcpyDeviceToHost));
+    *stats_out = st;
+    return CR_OK;
+}
+
+int cr_render_device(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, float *d_frame, void *stream) {
+    if (int rc = enter(c, false)) return rc;
+    return run_render(c, cam, p, d_frame, cr::MODE_BLEND, (hipStream_t)stream);
+}
+
+int cr_render_tiles_device(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, float *d_tiles,
+                           void *stream) {
+    if (int rc = enter(c, false)) return rc;
+    return run_render(c, cam, p, d_tiles, cr::MODE_TILES, (hipStream_t)stream);
+}
+
+uint32_t cr_layers_per_pass(cr_ctx *c, const cr_render_params *p, uint32_t want) {
+    if (!c || c->device < 0 || !c->has_scene || !p || want < 1 || check_params(c, p) != CR_OK) return 1;
+    if (c->kernel != 2 || c->wf_lanes != 1 || c->full_counters) return 1;
+    if (hipSetDevice(c->device) != hipSuccess) return 1;
+    const uint64_t items = (uint64_t)cr_tiles_for_rank(p, p->rank) * tile_of(p) * tile_of(p);
+    const uint64_t paths_cap = std::min<uint64_t>(c->wf_paths, wf_path_cap(c, p->k));
+    uint32_t nl = want;
+    while (nl > 1 && !cr::wf_layers_fit(items, p->spp, nl, paths_cap, c->sample_buf)) nl--;
+    return nl;
+}
+
+int cr_render_layers_device(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, uint32_t nlayers,
+                            float *d_frame, void *stream) {
+    if (int rc = enter(c, false)) return rc;
+    return run_render(c, cam, p, d_frame, cr::MODE_BLEND, (hipStream_t)stream, nlayers);
+}
+
+int cr_render_tiles_layers_device(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, uint32_t nlayers,
+                                  float *d_tiles, void *stream) {
+    if (int rc = enter(c, false)) return rc;
+    if (!p || p->nranks <= 1 || nlayers <= 1 || cr_layers_per_pass(c, p, nlayers) == nlayers)
+        return run_render(c, cam, p, d_tiles, cr::MODE_TILES, (hipStream_t)stream, nlayers);
+    // the rank's tiles in pieces (ranks r + kN of an N * m split: every tile slot keeps its pixels
+    // for any split of more than one rank), each written into the rank's compact buffer
+    uint32_t m = 1;
+    if (group_layers(c, p, nlayers, &m) != nlayers)
+        return fail(c, CR_E_INVALID, "layers per pass: the rank's share does not fit in pieces");
+    const uint64_t stride = (uint64_t)cr_tiles_for_rank(p, 0) * tile_of(p) * tile_of(p) * 3;
+    PassTotals sum;
+    for (uint32_t k = 0; k < m; k++) {
+        cr_render_params t = *p;
+        t.rank = p->rank + k * p->nranks;
+        t.nranks = p->nranks * m;
+        if (cr_tiles_for_rank(&t, t.rank) == 0) continue;
+        if (int rc = run_render(c, cam, &t, d_tiles, cr::MODE_TILES, (hipStream_t)stream, nlayers, k, m, stride))
+            return rc;
+        sum.add(c);
+    }
+    sum.store(c);
+    return CR_OK;
+}
+
+int cr_blend_tiles_device(cr_ctx *c, const cr_render_params *p, const float *d_gathered, float *d_frame,
+                          void *stream) {
+    return cr_blend_tiles_layers_device(c, p, 1, d_gathered, d_frame, stream);
+}
+
+int cr_blend_tiles_layers_device(cr_ctx *c, const cr_render_params *p, uint32_t nlayers, const float *d_gathered,
+                                 float *d_frame, void *stream) {
+    if (int rc = enter(c)) return rc;
+    if (!p || !d_gathered || !d_frame || p->nranks < 1 || p->layer < 1 || nlayers < 1)
+        return fail(c, CR_E_INVALID, "bad blend args");
+    cr::BlendArgs B = blend_args(p, d_gathered, d_frame);
+    B.nl = nlayers;
+    int e = cr::launch_blend(B, (hipStream_t)stream);
+    if (e) return hip_fail(c, (hipError_t)e, "blend kernel launch");
+    return CR_OK;
+}
+
+void cr_tonemap_setup(float exposure, float defog, float kneeLow, float kneeHigh, float gamma, cr_tonemap_params *t) {
+    if (!t) return;
+    t->m = powf(2.f, exposure + 2.47393f);
+    t->s = 255.f * powf(2.f, -3.5f * gamma);
+    t->kl = powf(2.f, kneeLow);
+    t->f = tm_find_knee_f(powf(2.f, kneeHigh), powf(2.f, 3.5) - t->kl);
+    t->defog = defog;
+    t->gamma = gamma;
+}
+
+int cr_tonemap_device(cr_ctx *c, const cr_tonemap_params *t, uint32_t xres, uint32_t yres, const float *d_rgb,
+                      uint8_t *d_bytes, void *stream) {
+    if (int rc = enter(c)) return rc;
+    if (!t || !d_rgb || !d_bytes) return fail(c, CR_E_INVALID, "bad tonemap args");
+    if ((uint64_t)xres * yres > (1ull << 31)) return fail(c, CR_E_INVALID, "image too large");
+    const cr::TonemapArgs T{d_rgb, d_bytes, xres, yres, t->m, t->s, t->kl, t->f, t->defog, t->gamma};
+    const int e = cr::launch_tonemap(T, (hipStream_t)stream);
+    if (e) return hip_fail(c, (hipError_t)e, "tonemap kernel launch");
+    return CR_OK;
+}
+
+int cr_tonemap(cr_ctx *c, const cr_tonemap_params *t, uint32_t xres, uint32_t yres, uint8_t *bytes_out) {
+    if (int rc = enter(c)) return rc;
+    if (!bytes_out) return fail(c, CR_E_INVALID, "null output");
+    const size_t n = (size_t)3 * xres * yres;
+    if (!c->d_accum.ptr || c->d_accum.count<float>() != n)
+        return fail(c, CR_E_INVALID, "no rendered frame of this size");
+    DevBuf bytes;
+    if (int r = grow(c, bytes, n ? n : 1, "tonemap buffer")) return r;
+    int rc = cr_tonemap_device(c, t, xres, yres, c->d_accum.as<float>(), bytes.as<uint8_t>(), c->stream);
+    if (rc == CR_OK) {
+        const hipError_t e = hipMemcpyAsync(bytes_out, bytes.ptr, n, hipMemcpyDeviceToHost, c->stream);
+        const hipError_t e2 = e == hipSuccess ? hipStreamSynchronize(c->stream) : e;
+        if (e2 != hipSuccess) rc = hip_fail(c, e2, "tonemap copy");
+    }
+    return rc;
+}
+
+int cr_intersect(cr_ctx *c, uint32_t n, const float *orig, const float *dir, uint32_t *hit, uint32_t *tri,
+                 float *bary, float *dist) {
+    return run_query(c, n, false, orig, dir, nullptr, nullptr, hit, tri, bary, dist);
+}
+
+int cr_intersect_shadow(cr_ctx *c, uint32_t n, const float *orig, const float *dir, const float *dist,
+                        const uint32_t *light_tri, uint32_t *occluded) {
+    if (c && n && (!dist || !light_tri)) return fail(c, CR_E_INVALID, "null dist/light");
+    return run_query(c, n, true, orig, dir, dist, light_tri, occluded, nullptr, nullptr, nullptr);
+}
+
 int cr_intersect_device(cr_ctx *c, uint32_t n, const float *d_orig, const float *d_dir, uint32_t *d_hit,
                         uint32_t *d_tri, float *d_bary, float *d_dist, void *stream) {
     return run_query_device(c, n, false, d_orig, d_dir, nullptr, nullptr, d_hit, d_tri, d_bary, d_dist, stream);
@@ -1388,71 +1067,20 @@ int cr_get_perf(cr_ctx *c, uint64_t *out, int n) {
 
 int cr_set_option(cr_ctx *c, const char *key, int64_t v) {
     if (!c || !key) return CR_E_INVALID;
-    const int64_t nvar = cr::num_wf_variants();
-    // (the megakernel (0) and the thread-per-pixel kernel (1) were measured slower and removed: DESIGN.md §3)
-    if (!std::strcmp(key, "kernel") && v == 2) c->kernel = (int)v;
-    else if (!std::strcmp(key, "counters") && (v == 0 || v == 1)) c->full_counters = (int)v;
-    else if (!std::strcmp(key, "perf_counters") && (v == 0 || v == 1)) c->perf_counters = (int)v;
-    else if (!std::strcmp(key, "wf_tail_overlap") && (v == 0 || v == 1)) c->wf_tail_overlap = (int)v;
-    else if (!std::strcmp(key, "wf_sort_g1") && v >= 0 && v <= 3) c->wf_sort_g1 = (uint32_t)v;
-    else if (!std::strcmp(key, "wf_cam_lean") && (v == 0 || v == 1)) c->wf_cam_lean = (int)v;
-    else if (!std::strcmp(key, "wf_cam_fuse") && (v == 0 || v == 1)) c->wf_cam_fuse = (int)v;
-    else if (!std::strcmp(key, "wf_ctl_ray") && (v == 0 || v == 1)) c->wf_ctl_ray = (int)v;
-    else if (!std::strcmp(key, "wf_vis_dw") && (v == 0 || v == 1)) c->wf_vis_dw = (int)v;
-    else if (!std::strcmp(key, "wf_vis_mark") && (v == 0 || v == 1)) c->wf_vis_mark = (int)v;
-    else if (!std::strcmp(key, "sum_lds") && v >= 0 && v <= 65536) c->sum_lds = (uint32_t)v;
-    else if (!std::strcmp(key, "wf_nee_skip") && (v == 0 || v == 1)) c->wf_nee_skip = (int)v;
-    else if (!std::strcmp(key, "sum_staged") && (v == 0 || v == 1)) c->sum_staged = (int)v;
-    else if (!std::strcmp(key, "wf_tail_waves") && v >= 4 && v <= 6) c->wf_tail_waves = (int)v;
-    else if (!std::strcmp(key, "wf_side_priority") && (v == 0 || v == 1)) {
+    // the one option with a side effect; every other is a row of ctxopts.hpp's table
+    if (!std::strcmp(key, "wf_side_priority") && (v == 0 || v == 1)) {
         // the second stream (closest trace g + 1 beside shadow trace g) at the device's highest
         // stream priority (1) or the default (0): which persistent grid takes the CUs first
         int lo = 0, hi = 0;
         if (hipSetDevice(c->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
             hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess)
             return CR_E_HIP;
-        hipStream_t s = nullptr;
-        if (hipStreamCreateWithPriority(&s, hipStreamNonBlocking, v ? hi : lo) != hipSuccess) return CR_E_HIP;
-        hipStreamDestroy(c->wfs.side);
-        c->wfs.side = s;
+        Stream s;
+        if (s.create(v ? hi : lo) != hipSuccess) return CR_E_HIP;
+        std::swap(c->side.h, s.h); // (the old stream goes with s)
+        return CR_OK;
     }
-    else if (!std::strcmp(key, "diag_kinds") && v >= 0 && v <= 7) c->diag_kinds = (uint32_t)v;
-    else if (!std::strcmp(key, "lc_debug") && v >= 0 && v <= 2) c->lc_debug = (int)v;
-    else if (!std::strcmp(key, "lc_min") && v >= 0 && v <= 33) c->lc_min = (uint32_t)v;
-    else if (!std::strcmp(key, "desc_quorum") && v >= -1 && v <= 64) c->desc_quorum = (int)v;
-    else if (!std::strcmp(key, "comm_timeout_ms") && v >= 1 && v <= 3600000) c->comm_timeout_ms = (uint32_t)v;
-    else if (!std::strcmp(key, "variant") && v >= -1 && v < nvar) c->variant = (int)v; // -1 default; clamped per kernel
-    else if (!std::strcmp(key, "refill") && v >= 0 && v <= 64) c->refill = (uint32_t)v; // 0: per-kernel default
-    else if (!std::strcmp(key, "refill_shadow") && v >= 0 && v <= 64) c->refill_shadow = (uint32_t)v;
-    else if (!std::strcmp(key, "refill_camera") && v >= 0 && v <= 64) c->refill_camera = (uint32_t)v;
-    else if (!std::strcmp(key, "wf_sort") && v >= -1 && v <= 1) c->wf_sort = (int)v;
-    else if (!std::strcmp(key, "wf_world_keys") && v >= 0 && v <= 64) c->wf_world_keys = (int)v;
-    else if (!std::strcmp(key, "wf_world_bits") && v >= 1 && v <= 10) c->wf_world_bits = (uint32_t)v;
-    else if (!std::strcmp(key, "wf_sort_min") && v >= 0 && v <= (1ll << 31)) c->wf_sort_min = (uint32_t)v;
-    else if (!std::strcmp(key, "wf_tail_min") && v >= 0 && v <= 0xffffffffll) c->wf_tail_min = (uint32_t)v;
-    else if (!std::strcmp(key, "wf_sort_tile") && v >= 0 && v <= 5) c->wf_sort_tile = (uint32_t)v;
-    else if (!std::strcmp(key, "wf_dir_res") && v >= 1 && v <= 256 && (v & (v - 1)) == 0)
-        c->wf_dir_res = (uint32_t)v;
-    else if (!std::strcmp(key, "wf_dir_res_shadow") && v >= 0 && v <= 256 && (v & (v - 1)) == 0)
-        c->wf_dir_res_shadow = (uint32_t)v;
-    else if (!std::strcmp(key, "wf_paths") && v >= 4096 && v <= (1ll << 30)) c->wf_paths = (uint32_t)v;
-    else if (!std::strcmp(key, "wf_lanes") && (v == 1 || v == 2)) c->wf_lanes = (int)v;
-    else if (!std::strcmp(key, "wf_xcd") && v >= 0 && v <= 7) c->wf_xcd = (uint32_t)v;
-    else if (!std::strcmp(key, "wf_leaf_keys") && (v == 0 || v == 1)) c->wf_leaf_keys = (int)v;
-    else if (!std::strcmp(key, "wf_resolve_paths") && v >= 0 && v <= 64) c->wf_resolve_paths = (uint32_t)v;
-    else if (!std::strcmp(key, "wf_measure_skip") && v >= 0 && v <= 3) c->wf_measure_skip = (uint32_t)v;
-    else if (!std::strcmp(key, "wf_shade_waves") && (v == 6 || v == 8)) c->wf_shade_waves = (int)v;
-    else if (!std::strcmp(key, "wf_shade_block") && (v == 256 || v == 512 || v == 1024)) c->wf_shade_block = (int)v;
-    else if (!std::strcmp(key, "wf_app_chunk") && (v == 0 || (v >= 256 && v <= 65536 && !(v & (v - 1))))) c->wf_app_chunk = (int)v;
-    else if (!std::strcmp(key, "wf_leaf_shift") && v >= 0 && v <= 24) c->wf_leaf_shift = (uint32_t)v;
-    else if (!std::strcmp(key, "wf_packet_unanimous") && (v == 0 || v == 1)) c->wf_packet_unanimous = (int)v;
-    else if (!std::strcmp(key, "node_bfs") && v >= 1 && v <= (1ll << 30)) c->node_bfs = (uint32_t)v;
-    else if (!std::strcmp(key, "sample_buf_bytes") && v >= 1 && v <= (1ll << 40)) c->sample_buf = (uint64_t)v;
-    else if (!std::strcmp(key, "query_route") && v >= 0 && v <= 2) c->query_route = (int)v;
-    else if (!std::strcmp(key, "query_sort") && v >= -1 && v <= 1) c->query_sort = (int)v;
-    else if (!std::strcmp(key, "query_chunk") && v >= 256 && v <= (1ll << 24)) c->query_chunk = (uint32_t)v;
-    else if (!std::strcmp(key, "query_trace_min") && v >= 0 && v <= 0xffffffffll) c->query_trace_min = (uint32_t)v;
-    else return fail(c, CR_E_INVALID, std::string("unknown option or value: ") + key);
+    if (!cr::set_option(*c, key, v)) return fail(c, CR_E_INVALID, std::string("unknown option or value: ") + key);
     return CR_OK;
 }
 
