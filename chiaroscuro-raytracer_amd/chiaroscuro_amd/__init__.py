@@ -177,6 +177,30 @@ class CrNoiseStats(C.Structure):
                 "layers": int(self.layers)}
 
 
+class CrAdaptiveParams(C.Structure):
+    """cr_adaptive_params (include/chiaro_hip.h "adaptive sampling")."""
+    _fields_ = [("min_layers", C.c_uint32), ("max_layers", C.c_uint32), ("check_every", C.c_uint32)]
+
+
+class CrSelectStats(C.Structure):
+    """cr_select_stats: non-skipped input entries, entries selected, the largest err, the layers the pixels hold."""
+    _fields_ = [("evaluated", C.c_uint64), ("above", C.c_uint64), ("max_err", C.c_float), ("layers", C.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {"evaluated": int(self.evaluated), "above": int(self.above), "max_err": float(self.max_err),
+                "layers": int(self.layers)}
+
+
+class CrAdaptiveStats(C.Structure):
+    """cr_adaptive_stats of a cr_render_adaptive."""
+    _fields_ = [("pixels", C.c_uint64), ("pixel_layers", C.c_uint64), ("active", C.c_uint64),
+                ("layers", C.c_uint32), ("checks", C.c_uint32), ("max_err", C.c_float)]
+
+    def as_dict(self) -> dict:
+        return {"pixels": int(self.pixels), "pixel_layers": int(self.pixel_layers), "active": int(self.active),
+                "layers": int(self.layers), "checks": int(self.checks), "max_err": float(self.max_err)}
+
+
 def tonemap_params(exposure, defog=0.0, knee_low=0.0, knee_high=5.0, gamma=2.2) -> CrTonemapParams:
     """cr_tonemap_setup: normalizeImage's host scalars (src/rayTracer.cpp:196-205)."""
     t = CrTonemapParams()
@@ -201,7 +225,9 @@ HIP_SYMBOLS = ("cr_create", "cr_destroy", "cr_last_error", "cr_upload_scene", "c
                "cr_render_tiles_layers_device", "cr_render_layers", "cr_scene_triangles", "cr_layers_per_group",
                "cr_blend_tiles_layers_device", "cr_render_dist_layers_device", "cr_group_render_layers",
                "cr_noise_struct_sizes", "cr_render_layers_noise_device", "cr_noise_device", "cr_render_layers_noise",
-               "cr_noise", "cr_set_noise_accumulator", "cr_render_until")
+               "cr_noise", "cr_set_noise_accumulator", "cr_render_until",
+               "cr_adaptive_struct_sizes", "cr_render_layers_list_device", "cr_noise_select_device",
+               "cr_render_adaptive")
 HOST_SYMBOLS = ("chiaro_last_error", "chiaro_scene_create", "chiaro_scene_info_get", "chiaro_scene_destroy",
                 "chiaro_model_create", "chiaro_model_load", "chiaro_model_num_meshes", "chiaro_model_num_triangles",
                 "chiaro_model_num_textures", "chiaro_model_triangles", "chiaro_model_texture",
@@ -218,11 +244,18 @@ HOST_SYMBOLS = ("chiaro_last_error", "chiaro_scene_create", "chiaro_scene_info_g
                 "chiaro_preview_create", "chiaro_preview_key", "chiaro_preview_mouse", "chiaro_preview_scroll",
                 "chiaro_preview_texture", "chiaro_preview_state", "chiaro_preview_destroy",
                 "chiaro_preview_camera_replay", "chiaro_raytracer_raytrace_until", "chiaro_raytracer_noise",
-                "chiaro_raytracer_noise_map", "chiaro_noise_struct_sizes")
+                "chiaro_raytracer_noise_map", "chiaro_noise_struct_sizes", "chiaro_raytracer_raytrace_adaptive",
+                "chiaro_raytracer_adaptive", "chiaro_raytracer_layer_map")
 
 P = C.c_void_p
 FP = C.POINTER(C.c_float)
 UP = C.POINTER(C.c_uint32)
+
+
+class CTX(C.c_void_p):
+    """The cr_ctx * of the adaptive-sampling entry points: c_void_p under a name of its own.  The order of the checks
+    at every entry point whose first argument type is P is pinned against a recording of the library from before
+    these existed (tests/golden/abi_errors_parent.json); theirs is pinned by tests/test_adaptive_abi.py."""
 
 
 def _sig(lib, name, res, args):
@@ -322,6 +355,14 @@ def libs():
     _sig(hip, "cr_set_noise_accumulator", C.c_int, [P, C.c_uint32, C.c_uint32, FP])
     _sig(hip, "cr_render_until", C.c_int, [P, C.POINTER(CrCamera), C.POINTER(CrRenderParams), C.c_uint32, C.c_uint32,
                                            C.c_uint32, NP, C.c_uint64, FP, NS])
+    _sig(hip, "cr_adaptive_struct_sizes", None, [UP, UP, UP])
+    _sig(hip, "cr_render_layers_list_device", C.c_int,
+         [CTX, C.POINTER(CrCamera), C.POINTER(CrRenderParams), C.c_uint32, P, C.c_uint32, P, P, P])
+    _sig(hip, "cr_noise_select_device", C.c_int,
+         [CTX, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, NP, P, P, P, C.c_uint32, P, P, P])
+    _sig(hip, "cr_render_adaptive", C.c_int,
+         [CTX, C.POINTER(CrCamera), C.POINTER(CrRenderParams), C.POINTER(CrAdaptiveParams), NP, FP, FP, UP,
+          C.POINTER(CrAdaptiveStats)])
 
     _sig(host, "chiaro_last_error", C.c_char_p, [])
     _sig(host, "chiaro_scene_create", P, [C.c_int, C.POINTER(C.c_char_p)])
@@ -350,6 +391,11 @@ def libs():
     _sig(host, "chiaro_raytracer_noise", C.c_int, [P, NS])
     _sig(host, "chiaro_raytracer_noise_map", C.c_int, [P, FP])
     _sig(host, "chiaro_noise_struct_sizes", None, [UP, UP])
+    _sig(host, "chiaro_raytracer_raytrace_adaptive", C.c_int, [P, C.c_float, C.c_uint32, FP, FP, FP, C.c_float,
+                                                               C.c_float, C.c_uint32, C.c_uint32,
+                                                               C.POINTER(C.c_uint64)])
+    _sig(host, "chiaro_raytracer_adaptive", C.c_int, [P, C.POINTER(CrAdaptiveStats)])
+    _sig(host, "chiaro_raytracer_layer_map", C.c_int, [P, UP])
     _sig(host, "chiaro_raytracer_pixels", FP, [P])
     _sig(host, "chiaro_raytracer_data", C.POINTER(C.c_uint8), [P])
     _sig(host, "chiaro_raytracer_maxval", C.c_float, [P])
@@ -622,6 +668,44 @@ class Device:
                                             int(check_every), C.byref(np_), int(max_above), _ptr(out), C.byref(st)),
                   "cr_render_until")
         return out, st.as_dict()
+
+    def render_layers_list(self, cam, p, nlayers: int, d_list_ptr: int, n_list: int, d_frame_ptr: int,
+                           d_m2_ptr: int = 0, stream: int = 0):
+        """cr_render_layers_list_device: layers p.layer .. + nlayers - 1 of the n_list pixels of the device pixel list
+        (uint32 indices y * xres + x; 0xffffffff: skipped) blended in place into the device frame, and into the
+        device moment frame when d_m2_ptr is given; no other pixel is touched."""
+        self._chk(libs()[0].cr_render_layers_list_device(self._c, C.byref(cam), C.byref(p), int(nlayers),
+                                                         C.c_void_p(d_list_ptr or None), int(n_list),
+                                                         C.c_void_p(d_frame_ptr), C.c_void_p(d_m2_ptr or None),
+                                                         C.c_void_p(stream)), "cr_render_layers_list_device")
+
+    def noise_select(self, xres: int, yres: int, layers: int, spp: int, threshold: float, floor: float,
+                     d_frame_ptr: int, d_m2_ptr: int, d_list_in_ptr: int, n_in: int, d_list_out_ptr: int,
+                     d_stats_ptr: int, stream: int = 0):
+        """cr_noise_select_device: the entries of the input list whose pixel's error is above threshold, in input
+        order, into d_list_out (room for n_in entries); d_stats: 24 bytes of device memory laid out as
+        CrSelectStats.  Enqueued on `stream`."""
+        np_ = CrNoiseParams(float(threshold), float(floor))
+        self._chk(libs()[0].cr_noise_select_device(self._c, int(xres), int(yres), int(layers), int(spp), C.byref(np_),
+                                                   C.c_void_p(d_frame_ptr), C.c_void_p(d_m2_ptr),
+                                                   C.c_void_p(d_list_in_ptr or None), int(n_in),
+                                                   C.c_void_p(d_list_out_ptr or None), C.c_void_p(d_stats_ptr),
+                                                   C.c_void_p(stream)), "cr_noise_select_device")
+
+    def render_adaptive(self, cam: CrCamera, p: CrRenderParams, min_layers: int, max_layers: int, check_every: int,
+                        threshold: float, floor: float, want_m2: bool = True):
+        """cr_render_adaptive: the frame from layer 1 with further layers only for the pixels whose error is above
+        threshold; returns (frame, m2 or None, layer map uint32 [yres][xres], stats dict)."""
+        out = np.zeros((p.yres, p.xres, 3), np.float32)
+        mom = np.zeros((p.yres, p.xres, 3), np.float32) if want_m2 else None
+        lmap = np.zeros((p.yres, p.xres), np.uint32)
+        np_ = CrNoiseParams(float(threshold), float(floor))
+        ap = CrAdaptiveParams(int(min_layers), int(max_layers), int(check_every))
+        st = CrAdaptiveStats()
+        self._chk(libs()[0].cr_render_adaptive(self._c, C.byref(cam), C.byref(p), C.byref(ap), C.byref(np_), _ptr(out),
+                                               _ptr(mom) if want_m2 else None, _ptr(lmap, C.c_uint32), C.byref(st)),
+                  "cr_render_adaptive")
+        return out, mom, lmap, st.as_dict()
 
     def render_device(self, cam, p, d_frame_ptr: int, stream: int = 0):
         self._chk(libs()[0].cr_render_device(self._c, C.byref(cam), C.byref(p), C.c_void_p(d_frame_ptr),
@@ -954,6 +1038,30 @@ class RayTracer:
         if rc:
             raise RuntimeError("rayTraceUntil: " + _host_err())
         return int(reached.value)
+
+    def rayTraceAdaptive(self, threshold, maxLayers, eye, center, up=(0.0, 1.0, 0.0), yview=1.0, floor=1e-3,
+                         minLayers=1, checkEvery=1) -> int:
+        """The view from layer 1 with further layers (at most maxLayers per pixel, checked every checkEvery from
+        minLayers on) only for the pixels whose relative error is above threshold; a pixel at or below it is frozen.
+        Returns the pixel-layers rendered; layerMap() is each pixel's count, lastAdaptive() the statistic."""
+        done = C.c_uint64(0)
+        rc = libs()[1].chiaro_raytracer_raytrace_adaptive(self._h, float(threshold), int(maxLayers), _fa(eye),
+                                                          _fa(center), _fa(up), float(yview), float(floor),
+                                                          int(minLayers), int(checkEvery), C.byref(done))
+        if rc:
+            raise RuntimeError("rayTraceAdaptive: " + _host_err())
+        return int(done.value)
+
+    def lastAdaptive(self) -> dict:
+        st = CrAdaptiveStats()
+        libs()[1].chiaro_raytracer_adaptive(self._h, C.byref(st))
+        return st.as_dict()
+
+    def layerMap(self) -> np.ndarray:
+        m = np.zeros((self.yres, self.xres), np.uint32)
+        if libs()[1].chiaro_raytracer_layer_map(self._h, _ptr(m, C.c_uint32)):
+            raise RuntimeError("layerMap: no adaptive render yet")
+        return m
 
     def lastNoise(self) -> dict:
         st = CrNoiseStats()

@@ -4,6 +4,7 @@
 // kernels.hip header), the progressive accumulator, the counters and the
 // per-launch HIP events.  No C++ exception or hipError_t crosses the ABI.
 #include "ctx.hpp"
+#include "adaptive.hpp"
 #include "scenelayout.hpp"
 #include "wfplan.hpp"
 
@@ -191,11 +192,14 @@ cr_counters counters_of(const unsigned long long *h) {
 }
 
 int run_render(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, float *out, int mode, hipStream_t st,
-               uint32_t nl, uint32_t piece_k, uint32_t piece_m, uint64_t stride, float *m2) {
+               uint32_t nl, uint32_t piece_k, uint32_t piece_m, uint64_t stride, float *m2, const uint32_t *list,
+               uint32_t list_items) {
     if (!cam || !out) return fail(c, CR_E_INVALID, "null camera/output");
     if (m2 && mode != cr::MODE_BLEND) return fail(c, CR_E_INVALID, "moments are tracked for blended frames only");
     int rc = check_params(c, p);
     if (rc) return rc;
+    if (list && (mode != cr::MODE_BLEND || p->nranks != 1 || !list_items || list_items % (tile_of(p) * tile_of(p))))
+        return fail(c, CR_E_INVALID, "a list pass blends whole tiles of entries into the frame");
     if (nl < 1 || (nl > 1 && (c->kernel != 2 || c->wf_lanes != 1)))
         return fail(c, CR_E_INVALID, "layers per pass: >= 1, and > 1 only with the wavefront kernel in one lane");
     HIPCHK(hipSetDevice(c->device));
@@ -203,6 +207,7 @@ int run_render(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, float
     fill_args(c, A, cam, p, out, mode);
     A.nl = nl;
     A.layer_stride = (uint64_t)cr_tiles_for_rank(p, 0) * A.tile * A.tile * 3;
+    if (list) A.list = list, A.n_items = list_items;
     if (piece_m > 1) {
         if (mode != cr::MODE_TILES || piece_k >= piece_m || !stride) return fail(c, CR_E_INVALID, "bad piece");
         A.piece_k = piece_k;
@@ -244,6 +249,9 @@ int run_render(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, float
     cr::WfArgs W2{};
     cr::wf_bind(in, pl, c->d_wf.ptr, A.gstack, 0, W);
     if (lanes == 2) cr::wf_bind(in, pl, c->d_wf2.ptr, A.gstack, 1, W2);
+    // a list pass runs the unfused camera path, whatever the options say: wf_camera_list makes the rays and writes
+    // generation 1's RNG state, and no trace, shade, resolve or tail kernel then derives a pixel from a work item
+    if (list) W.cam_fused = W.cam_lean = W.ctl_ray = W2.cam_fused = W2.cam_lean = W2.ctl_ray = 0;
     // screen-space cull boxes of this camera for the camera-ray trace (camcull.hpp),
     // computed inside the timed region of every render
     // (built for triangle-less scenes too: the culling kernels read them unconditionally, and
@@ -454,6 +462,66 @@ static int noise_of_accumulators(cr_ctx *c, uint32_t xres, uint32_t yres, uint32
     if (err_out)
         HIPCHK(hipMemcpyAsync(err_out, c->d_err.ptr, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
+    return CR_OK;
+}
+
+// ---- adaptive sampling ----
+// The selection of n_in entries of d_in into d_out on st, the statistic into *d_stats; nothing waits for it here
+static int enqueue_select(cr_ctx *c, uint32_t xres, uint32_t yres, uint32_t layers, uint32_t spp,
+                          const cr_noise_params *np, const float *d_frame, const float *d_m2, const uint32_t *d_in,
+                          uint32_t n_in, uint32_t *d_out, cr_select_stats *d_stats, hipStream_t st) {
+    HIPCHK(hipSetDevice(c->device));
+    if (int r = grow(c, c->d_select, cr::SELECT_SCRATCH * sizeof(uint32_t))) return r;
+    // the scratch is the ctx's: a selection on another stream waits for the last one
+    if (c->sel_pending && st != c->sel_stream) HIPCHK(hipStreamWaitEvent(st, c->sel_ev, 0));
+    cr::SelectArgs N{};
+    N.frame = d_frame;
+    N.m2 = d_m2;
+    N.in = d_in;
+    N.out = d_out;
+    N.stats = d_stats;
+    N.scratch = c->d_select.as<uint32_t>();
+    N.n_in = n_in;
+    N.npix = xres * yres;
+    N.layers = layers;
+    N.n = (float)(layers * spp);
+    N.threshold = np->threshold;
+    N.floor = np->floor;
+    const int e = cr::launch_noise_select(N, st);
+    const hipError_t ev = hipEventRecord(c->sel_ev, st);
+    c->sel_pending = ev == hipSuccess;
+    c->sel_stream = st;
+    if (e) return hip_fail(c, (hipError_t)e, "selection kernel launch");
+    if (ev != hipSuccess) return hip_fail(c, ev, "hipEventRecord(selection)");
+    return CR_OK;
+}
+// Layers q.layer .. + nlayers - 1 of the n_list entries of d_list blended into frame (and m2), as the passes of
+// ad_plan: each pass's entries are copied, padded with skipped ones to whole tiles, into d_list_pad.  The passes'
+// counters and times are added to `sum`.
+static int render_list(cr_ctx *c, const cr_camera *cam, const cr_render_params &q, uint32_t nlayers,
+                       const uint32_t *d_list, uint32_t n_list, float *frame, float *m2, hipStream_t st,
+                       crx::PassTotals &sum) {
+    cr::AdPlanIn in;
+    in.m = n_list;
+    in.n = nlayers;
+    in.spp = q.spp;
+    in.tile = tile_of(&q);
+    in.max_nl = c->kernel != 2 || c->wf_lanes != 1 || c->full_counters ? 1u : 32u; // (cr_layers_per_pass's rule)
+    in.paths_cap = std::min<uint64_t>(c->wf_paths, wf_path_cap(c, q.k));
+    in.sample_buf = c->sample_buf;
+    for (const cr::AdPass &ps : cr::ad_plan(in)) {
+        const uint32_t items = (uint32_t)cr::ad_padded(ps.count, in.tile);
+        if (int r = grow(c, c->d_list_pad, (size_t)items * sizeof(uint32_t))) return r;
+        HIPCHK(hipMemsetAsync(c->d_list_pad.ptr, 0xff, (size_t)items * sizeof(uint32_t), st)); // LIST_SKIP
+        HIPCHK(hipMemcpyAsync(c->d_list_pad.ptr, d_list + ps.first, (size_t)ps.count * sizeof(uint32_t),
+                              hipMemcpyDeviceToDevice, st));
+        cr_render_params t = q;
+        t.layer = q.layer + ps.layer0;
+        if (int rc = crx::run_render(c, cam, &t, frame, cr::MODE_BLEND, st, ps.nl, 0, 1, 0, m2,
+                                     c->d_list_pad.as<uint32_t>(), items))
+            return rc;
+        sum.add(c);
+    }
     return CR_OK;
 }
 
@@ -703,7 +771,7 @@ cr_ctx *cr_create(int device) {
         c->fork2.create(false) != hipSuccess || c->join2.create(false) != hipSuccess ||
         c->lane_ev[0].create(false) != hipSuccess || c->lane_ev[1].create(false) != hipSuccess ||
         c->hcnt.create(4) != hipSuccess || c->ev0.create(true) != hipSuccess || c->ev1.create(true) != hipSuccess ||
-        c->q_ev.create(false) != hipSuccess ||
+        c->q_ev.create(false) != hipSuccess || c->sel_ev.create(false) != hipSuccess ||
         c->d_counters.grow(cr::CTR_SLOTS * sizeof(unsigned long long)) != CR_OK) {
         delete c; // all or nothing: what was created goes now, while its device is current
         return (c = new cr_ctx())->err = "device init failed", c;
@@ -717,6 +785,7 @@ void cr_destroy(cr_ctx *c) {
         hipSetDevice(c->device);
         release_dist(c); // the communicator before its tile, gather and flag buffers
         if (c->q_pending) hipEventSynchronize(c->q_ev); // a pending query still uses d_query
+        if (c->sel_pending) hipEventSynchronize(c->sel_ev); // ... a pending selection d_select
     }
     delete c; // (a ctx without a device holds no handle: cr_create)
 }
@@ -903,6 +972,125 @@ int cr_render_until(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, 
     sum.store(c);
     HIPCHK(hipMemcpy(accum_rgb_out, c->d_accum.ptr, elems * sizeof(float), hipMemcpyDeviceToHost));
     *stats_out = st;
+    return CR_OK;
+}
+
+void cr_adaptive_struct_sizes(uint32_t *params_bytes, uint32_t *select_stats_bytes, uint32_t *stats_bytes) {
+    if (params_bytes) *params_bytes = (uint32_t)sizeof(cr_adaptive_params);
+    if (select_stats_bytes) *select_stats_bytes = (uint32_t)sizeof(cr_select_stats);
+    if (stats_bytes) *stats_bytes = (uint32_t)sizeof(cr_adaptive_stats);
+}
+
+int cr_render_layers_list_device(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, uint32_t nlayers,
+                                 const uint32_t *d_list, uint32_t n_list, float *d_frame, float *d_m2, void *stream) {
+    if (!c) return CR_E_INVALID;
+    if (!cam || !p || !d_frame || (!d_list && n_list) || nlayers < 1)
+        return fail(c, CR_E_INVALID, "null camera/params/frame/list or no layers");
+    if (n_list > (1u << 31)) return fail(c, CR_E_INVALID, "list too long");
+    if (int rc = enter(c)) return rc;
+    cr_render_params q = *p;
+    q.rank = 0, q.nranks = 1; // (the list is the share)
+    if (int rc = check_params(c, &q)) return rc;
+    if (n_list == 0) return CR_OK;
+    PassTotals sum;
+    if (int rc = render_list(c, cam, q, nlayers, d_list, n_list, d_frame, d_m2, (hipStream_t)stream, sum)) return rc;
+    sum.store(c);
+    return CR_OK;
+}
+
+int cr_noise_select_device(cr_ctx *c, uint32_t xres, uint32_t yres, uint32_t layers, uint32_t spp,
+                           const cr_noise_params *np, const float *d_frame, const float *d_m2, const uint32_t *d_list_in,
+                           uint32_t n_in, uint32_t *d_list_out, cr_select_stats *d_stats, void *stream) {
+    if (!c) return CR_E_INVALID;
+    if (!d_frame || !d_m2 || !d_stats || (n_in && (!d_list_in || !d_list_out)))
+        return fail(c, CR_E_INVALID, "null frame / moment frame / list / stats");
+    if (n_in > (1u << 31)) return fail(c, CR_E_INVALID, "list too long");
+    if (int r = check_noise_params(c, np)) return r;
+    if (int r = check_noise_shape(c, xres, yres, layers, spp)) return r;
+    if (int rc = enter(c, false)) return rc;
+    return enqueue_select(c, xres, yres, layers, spp, np, d_frame, d_m2, d_list_in, n_in, d_list_out, d_stats,
+                          (hipStream_t)stream);
+}
+
+int cr_render_adaptive(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, const cr_adaptive_params *ap,
+                       const cr_noise_params *np, float *frame_out, float *m2_out, uint32_t *layers_out,
+                       cr_adaptive_stats *stats_out) {
+    if (!c) return CR_E_INVALID;
+    if (!cam || !p || !ap || !frame_out || !stats_out)
+        return fail(c, CR_E_INVALID, "null camera/params/adaptive params/output/stats");
+    if (int r = check_noise_params(c, np)) return r;
+    if (ap->check_every < 1 || ap->max_layers < 1 || ap->min_layers > ap->max_layers)
+        return fail(c, CR_E_INVALID, "cr_render_adaptive: check_every >= 1 and min_layers <= max_layers, max_layers >= 1");
+    if (p->layer != 1) return fail(c, CR_E_INVALID, "cr_render_adaptive: renders from layer 1 (no resume: the layer map "
+                                                    "is not part of the accumulators)");
+    if (p->nranks > 1) return fail(c, CR_E_INVALID, "cr_render_adaptive: the whole frame (nranks 1)");
+    if ((uint64_t)ap->max_layers * p->spp > 0xFFFFFFFFull)
+        return fail(c, CR_E_INVALID, "max_layers * spp must fit 32 bits");
+    if (int rc = enter(c)) return rc;
+    cr_render_params q = *p;
+    q.rank = 0, q.nranks = 1;
+    int rc = check_params(c, &q);
+    if (rc) return rc;
+    if ((rc = check_noise_shape(c, q.xres, q.yres, ap->max_layers, q.spp))) return rc;
+    const uint32_t npix = q.xres * q.yres, T = tile_of(&q);
+    const uint32_t n_items = cr_tiles_for_rank(&q, 0) * T * T; // the frame's work items: the first list's entries
+    const size_t elems = (size_t)npix * 3;
+    if (int r = size_accumulator(c, c->d_accum, "accumulator", elems, true)) return r;
+    if (int r = size_accumulator(c, c->d_accum2, "moment accumulator", elems, true)) return r;
+    if (int r = grow(c, c->d_layer_map, (size_t)npix * sizeof(uint32_t))) return r;
+    if (int r = grow(c, c->d_sstats, sizeof(cr_select_stats))) return r;
+    for (DevBuf &b : c->d_active)
+        if (int r = grow(c, b, (size_t)n_items * sizeof(uint32_t))) return r;
+    float *frame = c->d_accum.as<float>(), *m2 = c->d_accum2.as<float>();
+    uint32_t *map = c->d_layer_map.as<uint32_t>();
+    PassTotals sum;
+    cr_adaptive_stats out{};
+    out.pixels = npix;
+    // the active set: the whole frame (list null: ordinary pass groups, the same bits on the fastest path) until the
+    // first pixel drops, then the list in d_active[cur], in the frame's work-item order
+    const uint32_t *list = nullptr;
+    uint32_t n_list = 0, cur = 0;
+    uint64_t active = npix;
+    for (uint32_t L = 0; L < ap->max_layers && active;) {
+        const cr::AdStep s = cr::ad_step(L, ap->min_layers, ap->max_layers, ap->check_every);
+        cr_render_params g = q;
+        g.layer = L + 1;
+        if ((rc = list ? render_list(c, cam, g, s.n, list, n_list, frame, m2, c->stream, sum)
+                       : render_layer_groups(c, cam, g, s.n, m2, sum)))
+            return rc;
+        L += s.n;
+        out.layers = L;
+        out.pixel_layers += active * s.n;
+        if (int e = cr::launch_list_fill(map, list, list ? n_list : npix, npix, L, c->stream))
+            return hip_fail(c, (hipError_t)e, "layer map kernel launch");
+        if (!s.check) continue;
+        if (!list) { // the first list: every work item of the frame
+            if (int e = cr::launch_tile_list(q.xres, q.yres, T, c->d_active[cur].as<uint32_t>(), c->stream))
+                return hip_fail(c, (hipError_t)e, "tile list kernel launch");
+        }
+        const uint32_t *in = list ? list : c->d_active[cur].as<uint32_t>();
+        uint32_t *sel = c->d_active[cur ^ 1].as<uint32_t>();
+        cr_select_stats st{};
+        if ((rc = enqueue_select(c, q.xres, q.yres, L, q.spp, np, frame, m2, in, list ? n_list : n_items, sel,
+                                 c->d_sstats.as<cr_select_stats>(), c->stream)))
+            return rc;
+        HIPCHK(hipMemcpyAsync(&st, c->d_sstats.ptr, sizeof(st), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        out.checks++;
+        out.active = st.above;
+        out.max_err = st.max_err;
+        if (L == ap->max_layers) break; // (the check served the statistic only)
+        if (st.above < active) { // pixels dropped: the selected ones are the new active set
+            list = sel, n_list = (uint32_t)st.above, cur ^= 1;
+            active = st.above;
+        }
+    }
+    sum.store(c);
+    HIPCHK(hipMemcpyAsync(frame_out, frame, elems * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (m2_out) HIPCHK(hipMemcpyAsync(m2_out, m2, elems * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (layers_out) HIPCHK(hipMemcpyAsync(layers_out, map, (size_t)npix * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *stats_out = out;
     return CR_OK;
 }
 

@@ -52,6 +52,14 @@ struct cr_ctx : cr::CtxOptions { // (the options, cr_set_option's table: ctxopts
     // d_accum, the squares' running sum beside d_run (sample-chunked passes), the error map and the device
     // statistic of cr_noise -- all grow-only
     crx::DevBuf d_accum2, d_run2, d_err, d_nstats;
+    // adaptive sampling (cr_render_layers_list_device / cr_noise_select_device / cr_render_adaptive), grow-only:
+    // a list pass's entries padded to whole tiles; the selection's scratch (cr::SELECT_SCRATCH words; sel_ev is
+    // recorded after each selection, and one on another stream than the last waits for it); the adaptive render's
+    // two active lists, its layer map and its device statistic
+    crx::DevBuf d_list_pad, d_select, d_active[2], d_layer_map, d_sstats;
+    crx::Event sel_ev;
+    bool sel_pending = false;
+    hipStream_t sel_stream = nullptr;
     crx::DevBuf d_cull;      // camera-ray cull boxes, one per leaf reference (+ 4), per render
     crx::DevBuf d_cull_node; // ... their per-leaf unions, one per kd node
     cr_counters last{};
@@ -103,9 +111,11 @@ cr::BlendArgs blend_args(const cr_render_params *p, const float *gathered, float
 // piece_m > 1 (MODE_TILES): p is piece piece_k of a rank's tiles (rank r + piece_k * N of an
 // N * piece_m split), written into the rank's compact buffer of layer stride `stride` floats
 // m2 (MODE_BLEND): the layers' second moments are blended into this moment frame beside `out`
+// list (MODE_BLEND, nranks 1): a list pass -- the work items are the list_items entries of the device pixel list
+// (RenderArgs::list; a multiple of tile * tile, padded with skipped entries), not p's tiles
 int run_render(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, float *out, int mode, hipStream_t st,
                uint32_t nl = 1, uint32_t piece_k = 0, uint32_t piece_m = 1, uint64_t stride = 0,
-               float *m2 = nullptr);
+               float *m2 = nullptr, const uint32_t *list = nullptr, uint32_t list_items = 0);
 // group.cpp: the communicator and buffers of the multi-process split (cr_destroy)
 void release_dist(cr_ctx *c);
 // The largest nl <= want (>= 1) whose paths fit one chunk when p's share (the frame for nranks 1, else rank

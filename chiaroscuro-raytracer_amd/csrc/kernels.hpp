@@ -160,7 +160,14 @@ struct RenderArgs {
     uint32_t lc_min;              // leaf-cull builds: leaves with fewer references are tested without the check
     uint32_t desc_quorum;         // lean wavefront traces: a round's descent stops once at most desc_quorum / 64
                                   // of its lanes still descend (they go on next round); 0: every lane reaches a leaf
+    // A list pass (cr_render_layers_list_device, MODE_BLEND): [n_items] work item i renders pixel index
+    // list[i] = y * xres + x of the frame; LIST_SKIP (or an index outside the frame) is no pixel -- a dead ray, as a
+    // partial-tile slot is.  null: the analytic tile mapping (item_pixel).  Read by wf_camera_list and the
+    // list forms of the sum kernels only: such a pass binds cam_fused, cam_lean and ctl_ray 0, and on that path no
+    // other kernel derives a pixel from a work item
+    const uint32_t *list;
 };
+enum : uint32_t { LIST_SKIP = 0xffffffffu };
 // Traversal-stack overflow area of a persistent trace grid of `threads` lanes: [depth][threads] x 8 B.
 inline size_t gstack_bytes(uint32_t depth, uint32_t threads) { return (size_t)depth * threads * 8; }
 // (SAMPLE_BUF_BYTES, the sample buffer budget: wfopts.hpp)
@@ -181,6 +188,28 @@ struct NoiseArgs {
     float n, threshold, floor; // n = (float)(layers * spp)
 };
 int launch_noise_eval(const NoiseArgs &N, hipStream_t st);
+// noise.hip: the selection of cr_noise_select_device -- the entries of `in` whose pixel's error is
+// above the threshold, in input order, into `out`, and the statistic.  Three launches in the sort's shape: every
+// block counts its contiguous range of the list, one block scans the counts, every block re-evaluates its range
+// and scatters.  No block waits for another, and there is no global atomic: the per-block counts and maxima go
+// through `scratch` [SELECT_SCRATCH] uint32 and the scan block reduces them.
+enum : uint32_t { SELECT_BLOCKS = 1024, SELECT_SCRATCH = 4 * SELECT_BLOCKS };
+struct SelectArgs {
+    const float *frame, *m2; // [npix][3]
+    const uint32_t *in;      // [n_in] pixel indices; LIST_SKIP (or an index >= npix) is skipped
+    uint32_t *out;           // [>= n_in]; the first `above` entries are written, nothing else
+    void *stats;             // cr_select_stats (device), written whole by the scan block
+    uint32_t *scratch;       // [SELECT_SCRATCH]
+    uint32_t n_in, npix, layers;
+    uint32_t per_block;      // list entries per block, a multiple of 256
+    float n, threshold, floor;
+};
+int launch_noise_select(SelectArgs N, hipStream_t st);
+// the frame's work-item order as a list: out[item] = the pixel of item under the analytic tile mapping of the whole
+// frame (LIST_SKIP for the slots of partial tiles outside it), n_items = tiles * tile * tile
+int launch_tile_list(uint32_t xres, uint32_t yres, uint32_t tile, uint32_t *out, hipStream_t st);
+// map[list[i]] = value for the n entries of list that are pixels (list null: map[i] = value for i < n)
+int launch_list_fill(uint32_t *map, const uint32_t *list, uint32_t n, uint32_t npix, uint32_t value, hipStream_t st);
 
 // Wavefront path tracer (wavefront.hip, cr_set_option "kernel" 2): the paths of
 // work items [w0, w0 + P) advance one bounce per generation through separate

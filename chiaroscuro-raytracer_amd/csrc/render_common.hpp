@@ -171,6 +171,19 @@ __device__ __forceinline__ bool item_pixel(const RenderArgs &A, uint32_t item, u
     return x < A.xres && y < A.yres;
 }
 
+// Work item -> pixel of a list pass (RenderArgs::list): the list's entry; LIST_SKIP, or an index outside the frame
+// (the caller's error, kept from the frame's memory here), is no pixel.
+// LIST false: item_pixel -- the kernels with a list form take the mapping as a template flag.
+template <bool LIST>
+__device__ __forceinline__ bool item_pixel_of(const RenderArgs &A, uint32_t item, uint32_t &x, uint32_t &y) {
+    if (!LIST) return item_pixel(A, item, x, y);
+    const uint32_t pix = A.list[item];
+    if (pix >= A.xres * A.yres) return false;
+    y = pix / A.xres;
+    x = pix - y * A.xres;
+    return true;
+}
+
 // The RNG stream of a path: pixel and sample s of this pass, which holds A.nl layers' samples as
 // one run per item (s / spp = the layer's offset from A.layer); A.nl = 1: the layer itself.
 __device__ __forceinline__ Rng path_rng(const RenderArgs &A, uint32_t pixel, uint32_t s) {

@@ -28,11 +28,13 @@ __device__ __forceinline__ void write_moment(const RenderArgs &A, float *m2, uin
 // rounded, then added, in the same order; carried across sample chunks in run2) and is blended into the moment
 // frame m2 wherever the sum is blended into the frame.  Without M2 the two pointers are unused and the
 // kernel's operations are the ones it always had.
-template <bool M2>
+// LIST (cr_render_layers_list_device): the item's pixel is the entry of A.list, not the tile mapping's
+// (item_pixel_of); the sums, their order and the blends are the same.
+template <bool M2, bool LIST = false>
 __global__ void __launch_bounds__(256) sum_samples(RenderArgs A, int first, int last, float *m2, float *run2) {
     const uint32_t item = blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t px = 0, py = 0;
-    const bool valid = item < A.n_items && item_pixel(A, item, px, py);
+    const bool valid = item < A.n_items && item_pixel_of<LIST>(A, item, px, py);
     if (valid) {
         f3 temp = mk(0.f, 0.f, 0.f);
         if (!first) temp = mk(A.run[3 * (size_t)item], A.run[3 * (size_t)item + 1], A.run[3 * (size_t)item + 2]);
@@ -86,13 +88,13 @@ __global__ void __launch_bounds__(256) sum_samples(RenderArgs A, int first, int 
 // waves streaming beside it have evicted it from L2 (2-3x the sample bytes at the fabric).  Needs
 // s_count % 4 == 0 (16-B aligned runs).
 enum : uint32_t { SUM_C = 16, SUM_ROW = 3 * SUM_C + 1 }; // (+1: the rows of consecutive pixels start in other banks)
-template <bool M2>
+template <bool M2, bool LIST = false>
 __global__ void __launch_bounds__(256) sum_samples_lds(RenderArgs A, int first, int last, float *m2, float *run2) {
     __shared__ float buf[256 * SUM_ROW];
     const uint32_t item0 = blockIdx.x * blockDim.x, item = item0 + threadIdx.x;
     const uint32_t nitems = min((uint32_t)blockDim.x, A.n_items - item0);
     uint32_t px = 0, py = 0;
-    const bool valid = item < A.n_items && item_pixel(A, item, px, py);
+    const bool valid = item < A.n_items && item_pixel_of<LIST>(A, item, px, py);
     f3 temp = mk(0.f, 0.f, 0.f);
     if (valid && !first) temp = mk(A.run[3 * (size_t)item], A.run[3 * (size_t)item + 1], A.run[3 * (size_t)item + 2]);
     f3 sq = mk(0.f, 0.f, 0.f); // (M2: the squares' sum, fed from the same staged values)
@@ -164,7 +166,16 @@ int launch_sum_samples(const RenderArgs &A, bool first, bool last, hipStream_t s
     if (!blocks) return (int)hipGetLastError();
     const int f = first ? 1 : 0, l = last ? 1 : 0;
     const bool lds_kernel = staged && A.s_count % 4 == 0;
-    if (m2 && lds_kernel)
+    if (A.list) { // a list pass: the same four kernels with the list's pixels
+        if (m2 && lds_kernel)
+            hipLaunchKernelGGL((sum_samples_lds<true, true>), dim3(blocks), dim3(256), lds, st, A, f, l, m2, run2);
+        else if (m2)
+            hipLaunchKernelGGL((sum_samples<true, true>), dim3(blocks), dim3(256), lds, st, A, f, l, m2, run2);
+        else if (lds_kernel)
+            hipLaunchKernelGGL((sum_samples_lds<false, true>), dim3(blocks), dim3(256), lds, st, A, f, l, m2, run2);
+        else
+            hipLaunchKernelGGL((sum_samples<false, true>), dim3(blocks), dim3(256), lds, st, A, f, l, m2, run2);
+    } else if (m2 && lds_kernel)
         hipLaunchKernelGGL(sum_samples_lds<true>, dim3(blocks), dim3(256), lds, st, A, f, l, m2, run2);
     else if (m2)
         hipLaunchKernelGGL(sum_samples<true>, dim3(blocks), dim3(256), lds, st, A, f, l, m2, run2);

@@ -6,7 +6,7 @@
 // (2 -> 6 waves/SIMD: 260 -> 563 Mray/s).  Here the same per-path arithmetic is
 // split by phase into kernels that exchange work through queues in HBM:
 //
-//   wf_camera                 one closest ray per path of the chunk
+//   wf_camera                 one closest ray per path of the chunk (wf_camera_list: of a list pass)
 //   wf_trace<closest>(1)
 //   for g = 1..K:
 //     wf_shade(g)             hit reconstruction, emission, NEE light sample
@@ -206,7 +206,9 @@ __device__ __forceinline__ Rng camera_rng(const RenderArgs &A, const WfArgs &W, 
 }
 
 // ---------------------------------------------------------------- camera --
-__global__ void __launch_bounds__(256) wf_camera(RenderArgs A, WfArgs W) {
+// LIST: a list pass (RenderArgs::list) -- the item's pixel is the list's entry, a skipped entry a dead ray
+template <bool LIST>
+__device__ __forceinline__ void camera_rays(const RenderArgs &A, const WfArgs &W) {
     __shared__ unsigned long long tl[T_N];
     if (threadIdx.x < T_N) tl[threadIdx.x] = 0;
     __syncthreads();
@@ -218,7 +220,7 @@ __global__ void __launch_bounds__(256) wf_camera(RenderArgs A, WfArgs W) {
         if (valid) {
             item = w / A.s_count;
             s = A.s0 + (w - item * A.s_count);
-            valid = item_pixel(A, item, px, py); // partial-tile pixels outside the image: no path
+            valid = item_pixel_of<LIST>(A, item, px, py); // partial-tile pixels outside the image: no path
         }
         tally(tl, T_PATHS, valid);
         // ray p of generation 1 is path p's camera ray (no compaction: the few
@@ -240,6 +242,8 @@ __global__ void __launch_bounds__(256) wf_camera(RenderArgs A, WfArgs W) {
     if (blockIdx.x == 0 && threadIdx.x == 0) *cnt_closest(W, 1) = W.P;
     flush_tallies(A, tl);
 }
+__global__ void __launch_bounds__(256) wf_camera(RenderArgs A, WfArgs W) { camera_rays<false>(A, W); }
+__global__ void __launch_bounds__(256) wf_camera_list(RenderArgs A, WfArgs W) { camera_rays<true>(A, W); }
 
 // The result of shadow query idx of generation g: occ[idx] or, with WfArgs::vis_dw, the w of the path's
 // dw record of bounce g (idx is then the path), which held the query's slot (SHADOW_VIS / SHADOW_OCC
@@ -1706,7 +1710,7 @@ struct ChunkLauncher {
         WfArgs &W = r.W;
         const WfStart s = wf_chunk_start(W, b->packet, A.eye_on_split != 0);
         W.cam_fused = s.cam_fused ? 1 : 0;
-        if (s.camera) hipLaunchKernelGGL(wf_camera, dim3(sgrid), dim3(256), 0, r.st, A, W);
+        if (s.camera) hipLaunchKernelGGL(A.list ? wf_camera_list : wf_camera, dim3(sgrid), dim3(256), 0, r.st, A, W);
         if (s.tail_only) tail(1, r.st, W);
         else closest(W, 1, r.st, nullptr, W.gstack); // camera rays: path order is already coherent
         r.g = 1, r.nin = W.P; // generation 1: one ray per path

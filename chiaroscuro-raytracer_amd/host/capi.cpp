@@ -309,6 +309,31 @@ int chiaro_raytracer_noise_map(chiaro_raytracer *r, float *err_out) {
         },
         CR_E_HIP);
 }
+int chiaro_raytracer_raytrace_adaptive(chiaro_raytracer *r, float threshold, uint32_t max_layers, const float eye[3],
+                                       const float center[3], const float up[3], float yview, float floor,
+                                       uint32_t min_layers, uint32_t check_every, uint64_t *pixel_layers_out) {
+    if (!r || !eye || !center || !up) return CR_E_INVALID;
+    return guard(
+        [&]() -> int {
+            const uint64_t done =
+                r->r->rayTraceAdaptive(threshold, max_layers, vec3(eye[0], eye[1], eye[2]),
+                                       vec3(center[0], center[1], center[2]), vec3(up[0], up[1], up[2]), yview, floor,
+                                       min_layers, check_every);
+            if (pixel_layers_out) *pixel_layers_out = done;
+            return CR_OK;
+        },
+        CR_E_HIP);
+}
+int chiaro_raytracer_adaptive(const chiaro_raytracer *r, cr_adaptive_stats *out) {
+    if (!r || !out) return CR_E_INVALID;
+    *out = r->r->lastAdaptive();
+    return CR_OK;
+}
+int chiaro_raytracer_layer_map(const chiaro_raytracer *r, uint32_t *layers_out) {
+    if (!r || !layers_out || r->r->layerMap().empty()) return CR_E_INVALID;
+    std::memcpy(layers_out, r->r->layerMap().data(), r->r->layerMap().size() * sizeof(uint32_t));
+    return CR_OK;
+}
 void chiaro_noise_struct_sizes(uint32_t *params_bytes, uint32_t *stats_bytes) {
     if (params_bytes) *params_bytes = (uint32_t)sizeof(cr_noise_params);
     if (stats_bytes) *stats_bytes = (uint32_t)sizeof(cr_noise_stats);

@@ -12,6 +12,8 @@
 // src/rayTracer.cpp:17-33, src/openglPreview.cpp:247-255).
 // Extra token "noise T" (this build): render until no pixel's relative error exceeds T
 // (RayTracer::rayTraceUntil); N of "layers N" is then the most layers to render.
+// Extra token "adaptive T" (this build): further layers only for the pixels whose relative error exceeds T
+// (RayTracer::rayTraceAdaptive); N of "layers N" is then the most layers of any pixel.
 #include "model.hpp"
 #include "raytracer.hpp"
 #include "scene.hpp"
@@ -26,7 +28,8 @@
 int main(int argc, char **argv) {
     // strip this build's own tokens before Scene sees them
     unsigned layers = 1;
-    float noise = -1.f; // "noise T": T >= 0
+    float noise = -1.f;    // "noise T": T >= 0
+    float adaptive = -1.f; // "adaptive T": T >= 0
     std::vector<char *> args;
     for (int i = 0; i < argc; i++) {
         if (i > 1 && !std::strcmp(argv[i], "layers") && i + 1 < argc) {
@@ -41,6 +44,14 @@ int main(int argc, char **argv) {
             }
             continue;
         }
+        if (i > 1 && !std::strcmp(argv[i], "adaptive") && i + 1 < argc) {
+            adaptive = (float)std::atof(argv[++i]);
+            if (!(adaptive >= 0.f)) {
+                std::fprintf(stderr, "chiaroscuro: adaptive takes a threshold >= 0\n");
+                return 1;
+            }
+            continue;
+        }
         args.push_back(argv[i]);
     }
     try {
@@ -51,7 +62,19 @@ int main(int argc, char **argv) {
         if (!model.error.empty()) std::fprintf(stderr, "%s\n", model.error.c_str());
         chiaro::RayTracer renderer(model, scene);
         // the layers in pass groups (RayTracer::rayTraceLayers, bit-identical to one rayTrace per layer)
-        if (noise >= 0.f) {
+        if (adaptive >= 0.f && noise >= 0.f) {
+            std::fprintf(stderr, "chiaroscuro: noise and adaptive exclude each other\n");
+            return 1;
+        }
+        if (adaptive >= 0.f) {
+            const unsigned long long done =
+                renderer.rayTraceAdaptive(adaptive, layers, scene.VP, scene.LA, scene.UP, scene.yview);
+            const cr_adaptive_stats &st = renderer.lastAdaptive();
+            std::fprintf(stderr, "adaptive %g: %llu of %llu pixel-layers rendered, %u checks, %llu pixels still above, "
+                                 "max error %g\n",
+                         adaptive, done, (unsigned long long)st.pixels * layers, st.checks,
+                         (unsigned long long)st.active, st.max_err);
+        } else if (noise >= 0.f) {
             const unsigned reached = renderer.rayTraceUntil(noise, layers, scene.VP, scene.LA, scene.UP, scene.yview);
             const cr_noise_stats &st = renderer.lastNoise();
             std::fprintf(stderr, "noise %g: layer %u of at most %u reached, %llu of %llu pixels above, max error %g (%s)\n",

@@ -106,6 +106,7 @@ void RayTracer::rayTrace(vec3 eye, vec3 center, vec3 up, float yview) { rayTrace
 void RayTracer::rayTraceLayers(unsigned n, vec3 eye, vec3 center, vec3 up, float yview) {
     if (n < 1) return;
     noiseTracked_ = false; // (these layers keep no moments: a later rayTraceUntil starts over)
+    mixedLayers_ = false;
     // rayTracer.cpp:24 -- including the reference's `(lastUp == lastUp)`: a
     // change of `up` alone does not reset the accumulation.
     const bool newLayer = (eye == lastEye) && (center == lastCenter) && (lastUp == lastUp) && (yview == lastYview);
@@ -180,6 +181,7 @@ unsigned RayTracer::rayTraceUntil(float threshold, unsigned maxLayers, vec3 eye,
     const bool newLayer = noiseTracked_ && (eye == lastEye) && (center == lastCenter) && (lastUp == lastUp) &&
                           (yview == lastYview);
     if (newLayer && layers_ >= maxLayers) return layers_;
+    mixedLayers_ = false;
     const unsigned first = newLayer ? layers_ + 1 : 1;
     if (!newLayer) {
         lastEye = eye;
@@ -221,6 +223,47 @@ unsigned RayTracer::rayTraceUntil(float threshold, unsigned maxLayers, vec3 eye,
     return layers_;
 }
 
+uint64_t RayTracer::rayTraceAdaptive(float threshold, unsigned maxLayers, vec3 eye, vec3 center, vec3 up, float yview,
+                                     float floor, unsigned minLayers, unsigned checkEvery) {
+    if (group_) throw std::runtime_error("chiaro: rayTraceAdaptive renders on one GPU (gpus 1)");
+    const auto t0 = std::chrono::high_resolution_clock::now();
+    const cr_camera cam = make_camera(eye, center, up, yview, scene.xres, scene.yres);
+    cr_render_params p{};
+    p.xres = scene.xres;
+    p.yres = scene.yres;
+    p.spp = scene.samples;
+    p.k = scene.k;
+    p.background[0] = scene.background.x;
+    p.background[1] = scene.background.y;
+    p.background[2] = scene.background.z;
+    p.seed = scene.seed;
+    p.layer = 1;
+    p.rank = 0;
+    p.nranks = 1;
+    p.tile = 32;
+    const cr_noise_params np{threshold, floor};
+    const cr_adaptive_params ap{minLayers, maxLayers, checkEvery};
+    // the frame is no progressive state, before or after: whatever follows starts at layer 1
+    layers_ = 0;
+    noiseTracked_ = false;
+    lastEye = lastCenter = lastUp = vec3(FLT_MAX);
+    lastYview = -1;
+    layerMap_.assign((size_t)scene.xres * scene.yres, 0u);
+    cr_adaptive_stats st{};
+    if (cr_render_adaptive(ctx_, &cam, &p, &ap, &np, pixels.data(), nullptr, layerMap_.data(), &st) != CR_OK) {
+        layerMap_.clear();
+        throw std::runtime_error(std::string("chiaro: render failed: ") + cr_last_error(ctx_));
+    }
+    layers_ = st.layers;
+    mixedLayers_ = true;
+    adaptive_ = st;
+    cr_get_counters(ctx_, &counters_);
+    maxVal = 0.f;
+    for (float v : pixels) maxVal = maxVal > v ? maxVal : v;
+    lastSeconds_ = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
+    return st.pixel_layers;
+}
+
 std::vector<float> RayTracer::noiseMap() {
     if (!noiseTracked_) throw std::runtime_error("chiaro: noiseMap: the frame is not a rayTraceUntil render");
     std::vector<float> err((size_t)scene.xres * scene.yres);
@@ -234,6 +277,7 @@ uint8_t *RayTracer::getData() { return data.data(); }
 
 void RayTracer::saveCheckpoint(const char *path) const {
     if (!layers_) throw std::runtime_error("checkpoint: nothing rendered yet");
+    if (mixedLayers_) throw std::runtime_error("checkpoint: an adaptive frame holds no single layer count to resume from");
     chiaro_checkpoint h{};
     h.xres = scene.xres;
     h.yres = scene.yres;
@@ -271,6 +315,7 @@ void RayTracer::resume(const char *path) {
     if (rc != CR_OK)
         throw std::runtime_error(std::string("resume: ") + (group_ ? cr_group_last_error(group_) : cr_last_error(ctx_)));
     layers_ = h.layers;
+    mixedLayers_ = false;
     noiseTracked_ = false; // (the checkpoint holds the frame only)
     lastEye = vec3(h.eye[0], h.eye[1], h.eye[2]);
     lastCenter = vec3(h.center[0], h.center[1], h.center[2]);

@@ -46,6 +46,17 @@ class RayTracer {
      * target was met.  One GPU only: with gpus > 1 it throws std::runtime_error. */
     unsigned rayTraceUntil(float threshold, unsigned maxLayers, vec3 eye, vec3 center, vec3 up = vec3(0.f, 1.f, 0.f),
                            float yview = 1.f, float floor = 1e-3f, unsigned checkEvery = 4, uint64_t maxAbove = 0);
+    /* This build: adaptive sampling (cr_render_adaptive, include/chiaro_hip.h "adaptive sampling"): the view rendered
+     * from layer 1, the noise checked every checkEvery layers from minLayers on, and further layers -- at most
+     * maxLayers per pixel -- spent only on the pixels whose relative error is still above threshold.  A pixel at or
+     * below it is frozen and never re-enters; minLayers guards against freezing on the estimate's low bias at few
+     * samples.  Returns the pixel-layers rendered (of xres * yres * maxLayers); layerMap() is each pixel's layer
+     * count, lastAdaptive() the statistic.  The frame then holds pixels of different layer counts: it is not a
+     * progressive state -- the next rayTrace* call starts at layer 1, and saveCheckpoint refuses it.  One GPU only. */
+    uint64_t rayTraceAdaptive(float threshold, unsigned maxLayers, vec3 eye, vec3 center, vec3 up = vec3(0.f, 1.f, 0.f),
+                              float yview = 1.f, float floor = 1e-3f, unsigned minLayers = 1, unsigned checkEvery = 1);
+    const std::vector<uint32_t> &layerMap() const { return layerMap_; } // [yres][xres]; empty before rayTraceAdaptive
+    const cr_adaptive_stats &lastAdaptive() const { return adaptive_; }
     /* The statistic of the last rayTraceUntil's last check, and the error map [yres][xres] of its frame. */
     const cr_noise_stats &lastNoise() const { return noise_; }
     std::vector<float> noiseMap();
@@ -83,6 +94,9 @@ class RayTracer {
     cr_noise_stats noise_{};
     cr_noise_params noiseParams_{0.f, 0.f}; // of the last rayTraceUntil (floor 0: none yet)
     bool noiseTracked_ = false;             // every layer of the frame came from rayTraceUntil (moments complete)
+    cr_adaptive_stats adaptive_{};
+    std::vector<uint32_t> layerMap_;
+    bool mixedLayers_ = false; // the frame is rayTraceAdaptive's: its pixels hold different layer counts
     double lastSeconds_ = 0.0;
     // rayTracer.cpp:18-22 progressive-layer state (per instance here, not function-static)
     unsigned layers_ = 0;

@@ -39,6 +39,10 @@
  *                        sample loop and blend (:59-64) with a second-moment frame kept beside the
  *                        frame, a per-pixel error from the two, and a render that stops at a noise
  *                        target (no reference counterpart: its callers fix the layer count).
+ *   cr_render_layers_list_device / cr_noise_select_device / cr_render_adaptive
+ *                        the same accumulation with further layers rendered only for the pixels that are still
+ *                        noisy: a render of listed pixels, the selection of the pixels above a threshold, and the
+ *                        loop of the two (no reference counterpart: its sample loop covers every pixel, :55-58).
  *   cr_intersect         KDTree::intersectRay       (src/kdtree.cpp:210-216)
  *   cr_intersect_shadow  KDTree::intersectShadowRay (src/kdtree.cpp:283-290)
  *   cr_intersect_device / cr_intersect_shadow_device
@@ -330,6 +334,87 @@ int cr_set_noise_accumulator(cr_ctx *ctx, uint32_t xres, uint32_t yres, const fl
 int cr_render_until(cr_ctx *ctx, const cr_camera *cam, const cr_render_params *p, uint32_t min_layers,
                     uint32_t max_layers, uint32_t check_every, const cr_noise_params *np, uint64_t max_above,
                     float *accum_rgb_out, cr_noise_stats *stats_out);
+
+/* --------------------------------------------------- adaptive sampling --
+ * cr_render_until stops for the whole frame; these calls spend further layers only on the pixels that are still
+ * noisy.  Every path's RNG stream is a function of (seed, layer, pixel, sample) alone, so a pixel's value does not
+ * depend on which other pixels share its pass, and everything below is defined bit for bit.
+ *
+ * PIXEL LIST: a device array of uint32.  Each entry is a pixel index y * xres + x of the frame, or 0xffffffff, an
+ * entry that is skipped (padding).  Entries are distinct; duplicates are the caller's error and undefined.  (An
+ * index outside the frame is the caller's error too; the kernels treat it as skipped.)
+ *
+ * LIST RENDER (cr_render_layers_list_device): renders layers p->layer .. p->layer + nlayers - 1 for the listed pixels
+ * only and blends them in place into d_frame, and into d_m2 when it is given, with the arithmetic of a full render.
+ * No other pixel of either frame is read or written.  A listed pixel then holds, bit for bit, what
+ * cr_render_layers_noise_device of the same layers leaves at that pixel; for p->layer > 1 the caller guarantees that
+ * the listed pixels hold layer p->layer - 1.  p->rank / p->nranks are not used (the list is the share).  A list of
+ * any length and any nlayers: what does not fit one pass runs as several (csrc/adaptive.hpp), on `stream`, and the
+ * call returns when they are complete; counters, cr_last_kernel_ms and the trace stats sum over them.
+ * n_list == 0: CR_OK, nothing launched.
+ *
+ * SELECTION (cr_noise_select_device): the inputs are (d_frame, d_m2), a list of n_in pixels that all hold `layers`
+ * layers, and cr_noise_params.  Each listed pixel's err is the noise block's formula with n = (float)(layers * spp):
+ * same operations, same order, a NaN counts as 0.  d_list_out (room for n_in entries; must not alias d_list_in)
+ * receives the input entries with err > threshold IN INPUT ORDER -- a stable compaction; skipped entries are
+ * dropped; nothing is written past `above` entries.  The statistic: `evaluated` (the non-skipped input entries),
+ * `above` (the output's length), `max_err` (the largest err of the evaluated pixels, 0 when none is positive) and
+ * `layers`, written through -- counts and a maximum, independent of the order of any reduction.  Stream-ordered on
+ * `stream`, no host synchronisation, needs no scene; *d_stats is device memory.  The call uses a small scratch of
+ * the ctx: a call on another stream than the last one first waits (on the device) for that one.
+ *
+ * ADAPTIVE RENDER (cr_render_adaptive): the whole frame from layer 1 on the ctx's accumulators.
+ *   1. L = 0; every pixel of the frame is active.
+ *   2. Render layers L+1 .. L+n for the active pixels, n = min(check_every, max_layers - L); L += n; every active
+ *      pixel's entry of the layer map becomes L.
+ *   3. If L < min_layers, go to 2 without a check.
+ *   4. Check: the selection over the active pixels at L.  If L == max_layers, stop (the check serves the statistic
+ *      only).  Otherwise the selected pixels are the new active set; if none is left, stop; else go to 2.
+ * Checks therefore happen at the multiples of check_every that are >= min_layers, and at max_layers -- whatever fits
+ * a pass: n layers that do not fit one pass run as several with no check between them, so the schedule, and with it
+ * every pixel's result, does not depend on free memory.  A pixel that drops out is FROZEN: it never re-enters, even
+ * if a later estimate of it would be above the threshold.  The estimate is biased low at few samples (a pixel whose
+ * first samples happen to agree looks converged; DESIGN.md 3.20, limit 2): min_layers is the guard against freezing
+ * on it.  The frame and the moment frame at pixel (x, y) are, bit for bit, those of cr_render_layers_noise after
+ * map[y][x] layers.  While no pixel has dropped the layers run as cr_render_layers_noise's own pass groups; after
+ * the first drop as list renders, in the frame's work-item order (tile-major, p->tile).
+ * Errors (arguments first, then the device, then the scene): CR_E_INVALID for a null pointer, check_every == 0,
+ * max_layers < 1, min_layers > max_layers, p->layer != 1 (a resumed render would need the layer map), nranks != 1,
+ * bad noise params, max_layers * spp above 32 bits.
+ * Not covered: MODE_TILES (cr_render_tiles_*), cr_group_*, cr_comm_* and the distributed renders.  The checkpoint
+ * format is unchanged (it holds no layer map: a frame of mixed layer counts cannot be resumed from it). */
+typedef struct cr_adaptive_params {
+    uint32_t min_layers;  /* no check, and no pixel frozen, before this many layers */
+    uint32_t max_layers;  /* the most layers of any pixel (>= 1, >= min_layers) */
+    uint32_t check_every; /* layers between checks (>= 1) */
+} cr_adaptive_params;
+typedef struct cr_select_stats {
+    uint64_t evaluated; /* non-skipped input entries */
+    uint64_t above;     /* entries selected = the output list's length */
+    float max_err;      /* largest err of the evaluated pixels */
+    uint32_t layers;    /* the layers the pixels hold, written through */
+} cr_select_stats;
+typedef struct cr_adaptive_stats {
+    uint64_t pixels;       /* xres * yres */
+    uint64_t pixel_layers; /* the sum of the layer map: what was rendered, of pixels * max_layers */
+    uint64_t active;       /* `above` of the last check (0 if none ran) */
+    uint32_t layers;       /* the last L */
+    uint32_t checks;       /* checks run */
+    float max_err;         /* of the last check (0 if none ran) */
+} cr_adaptive_stats;
+/* sizeof the three structures as this library was built */
+void cr_adaptive_struct_sizes(uint32_t *params_bytes, uint32_t *select_stats_bytes, uint32_t *stats_bytes);
+int cr_render_layers_list_device(cr_ctx *ctx, const cr_camera *cam, const cr_render_params *p, uint32_t nlayers,
+                                 const uint32_t *d_list, uint32_t n_list, float *d_frame, float *d_m2 /* may be null */,
+                                 void *stream);
+int cr_noise_select_device(cr_ctx *ctx, uint32_t xres, uint32_t yres, uint32_t layers, uint32_t spp,
+                           const cr_noise_params *np, const float *d_frame, const float *d_m2,
+                           const uint32_t *d_list_in, uint32_t n_in, uint32_t *d_list_out, cr_select_stats *d_stats,
+                           void *stream);
+/* frame_out [yres][xres][3]; m2_out [yres][xres][3] and layers_out (the layer map, uint32 [yres][xres]) may be null */
+int cr_render_adaptive(cr_ctx *ctx, const cr_camera *cam, const cr_render_params *p, const cr_adaptive_params *ap,
+                       const cr_noise_params *np, float *frame_out, float *m2_out, uint32_t *layers_out,
+                       cr_adaptive_stats *stats_out);
 
 /* Ray queries (host arrays). dir need not be normalised (the reference does not). */
 int cr_intersect(cr_ctx *ctx, uint32_t n, const float *orig, const float *dir, uint32_t *hit, uint32_t *tri,

@@ -8,6 +8,9 @@
  *   chiaro_raytracer_create  RayTracer::RayTracer(Model&, Scene&)  src/rayTracer.cpp:13-15
  *                            (builds KDTree, src/kdtree.cpp:34-108, uploads via cr_upload_scene)
  *   chiaro_raytracer_raytrace RayTracer::rayTrace                  src/rayTracer.cpp:17-74
+ *   chiaro_raytracer_raytrace_adaptive / _adaptive / _layer_map
+ *                            the same accumulation with further layers only where the frame is still noisy (this
+ *                            build; cr_render_adaptive)
  *   chiaro_raytracer_raytrace_until / _noise / _noise_map
  *                            rayTrace repeated until a noise target is met (this build; the accumulation of
  *                            src/rayTracer.cpp:18-33,59-64 with a second-moment frame, cr_render_until)
@@ -98,6 +101,19 @@ int chiaro_raytracer_raytrace_until(chiaro_raytracer *r, float threshold, uint32
 int chiaro_raytracer_noise(const chiaro_raytracer *r, cr_noise_stats *out);
 int chiaro_raytracer_noise_map(chiaro_raytracer *r, float *err_out);
 void chiaro_noise_struct_sizes(uint32_t *params_bytes, uint32_t *stats_bytes);
+/* RayTracer::rayTraceAdaptive: the view rendered from layer 1 with further layers -- at most max_layers per pixel,
+ * the noise checked every check_every layers from min_layers on -- spent only on the pixels whose relative error is
+ * still above threshold (cr_render_adaptive, include/chiaro_hip.h "adaptive sampling"; a pixel at or below it is
+ * frozen for good, min_layers guards against freezing on too few samples).  *pixel_layers_out (may be NULL): the
+ * pixel-layers rendered, of xres * yres * max_layers.  The frame is then no progressive state: the next raytrace
+ * call starts at layer 1 and chiaro_raytracer_checkpoint refuses it.  One GPU only.
+ * chiaro_raytracer_adaptive: the statistic of that render; chiaro_raytracer_layer_map: each pixel's layer count,
+ * uint32 [yres][xres] (CR_E_INVALID before the first adaptive render). */
+int chiaro_raytracer_raytrace_adaptive(chiaro_raytracer *r, float threshold, uint32_t max_layers, const float eye[3],
+                                       const float center[3], const float up[3], float yview, float floor,
+                                       uint32_t min_layers, uint32_t check_every, uint64_t *pixel_layers_out);
+int chiaro_raytracer_adaptive(const chiaro_raytracer *r, cr_adaptive_stats *out);
+int chiaro_raytracer_layer_map(const chiaro_raytracer *r, uint32_t *layers_out);
 const float *chiaro_raytracer_pixels(const chiaro_raytracer *r);
 const uint8_t *chiaro_raytracer_data(chiaro_raytracer *r);
 float chiaro_raytracer_maxval(const chiaro_raytracer *r);
