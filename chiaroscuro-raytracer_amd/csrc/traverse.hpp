@@ -1,8 +1,12 @@
 // traverse.hpp -- the resumable kd traversal of the wavefront trace kernels and the tail kernel
-// (wavefront.hip).
+// (wavefront.hip): the loads (sload_*, load_*, leaf_mask), the stack's pop (trav_pop), one kd decision
+// (kd_step), one triangle test (tri_one), the round that runs them (trav_round: descent, leaf references,
+// one leaf tester, the round's end) and the leaf exchange of the LX builds (leaf_exchange).  What only counts
+// or pads is behind Probe<C> (travprobe.hpp).  DESIGN.md §3.24 maps the round's stages to the C:: knobs and
+// the builds, and says how a change here is held to the parent's code (scripts/kernel_regs.py --diff).
 #pragma once
 #include "leafcull.hpp"
-#include "render_common.hpp"
+#include "travprobe.hpp"
 #include "wfbuilds.hpp"
 
 namespace cr {
@@ -19,23 +23,6 @@ enum : uint32_t {
     ST_LEAFX = 9,     // LX builds: the lane's leaf tests wait for the wave's leaf exchange (leaf_exchange)
 };
 
-// True when every active lane holds the same x.
-__device__ __forceinline__ bool wave_uniform(uint32_t x) {
-    return __ballot(x == (uint32_t)__builtin_amdgcn_readfirstlane(x)) == __ballot(1);
-}
-
-// Distinct values of key over the active lanes (FULL-build diagnostics).
-__device__ __forceinline__ uint32_t wave_distinct(uint32_t key) {
-    uint64_t m = __ballot(1);
-    uint32_t n = 0;
-    while (m) {
-        const uint32_t k = (uint32_t)__shfl((int)key, __ffsll((long long)m) - 1, 64);
-        m &= ~__ballot(key == k);
-        n++;
-    }
-    return n;
-}
-
 // Traversal registers of a query in flight.  r = per-axis rcp_for_div(d) for
 // the exact short split-distance division (FD builds, device_math.hpp).
 struct Trav {
@@ -43,56 +30,6 @@ struct Trav {
     float tmin, tmax;
     f3 r;
 };
-
-// Counting-build diagnostics of one lane (DIAG_* in kernels.hpp): the lane's last 8
-// triangles that missed for any segment in its current query (a per-lane mailbox, as a
-// census: no test is skipped), and its tallies (wave-level ones kept by the leader).
-struct Diag {
-    bool on;        // the trace kind is in RenderArgs::diag_kinds
-    uint32_t n;     // misses recorded in this query (reset at each query start)
-    uint32_t mb[8]; // mb[i & 7]: the i-th
-    uint32_t v[DIAG_N];
-};
-__device__ __forceinline__ void diag_begin(Diag *dg) {
-    if (dg) dg->n = 0;
-}
-__device__ __forceinline__ void diag_flush(unsigned long long *ctrs, const Diag &dg) {
-    const uint32_t ln = lane_id();
-#pragma unroll
-    for (int i = 0; i < DIAG_N; i++) {
-        unsigned long long s = dg.v[i];
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
-        if (ln == 0 && s) atomicAdd(&ctrs[CTR_DIAG + i], s);
-    }
-}
-
-// Performed work of one lane (perf builds, PERF_* in kernels.hpp): what the kernel executes and
-// the bytes its loads and stores move -- vector accesses per lane, scalar loads once per wave
-// (counted by the wave's leader).
-struct Pc {
-    uint32_t q, steps, leaves, masks, tests, waves;
-    uint64_t vb, sb;
-    uint32_t drounds, diters, dlanes, dtests;
-};
-__device__ __forceinline__ void pc_load(Pc *pc, bool scalar, uint32_t bytes) {
-    if (!pc) return;
-    if (!scalar) pc->vb += bytes;
-    else if (wave_leader()) pc->sb += bytes;
-}
-// Call with the whole wave converged: the lane sums go to ctrs[0 .. PERF_N).
-__device__ __forceinline__ void pc_flush(unsigned long long *ctrs, const Pc &pc) {
-    const uint32_t ln = lane_id();
-    const unsigned long long v[PERF_N] = {pc.q,     pc.steps,   pc.leaves, pc.masks,  pc.tests,  pc.vb,
-                                          pc.sb,    pc.waves,   pc.drounds, pc.diters, pc.dlanes, pc.dtests};
-#pragma unroll
-    for (int i = 0; i < PERF_N; i++) {
-        unsigned long long x = v[i];
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off, 64);
-        if (ln == 0 && x) atomicAdd(&ctrs[i], x);
-    }
-}
 
 // A lane's stack-overflow entry at `depth` ([depth][gstride] rows): a 32-bit byte offset from the
 // wave-uniform base, so the access uses scalar-base addressing and no 64-bit per-lane pointer is kept
@@ -118,14 +55,7 @@ __device__ __forceinline__ bool trav_begin(const DevScene &S, f3 o, f3 d, bool s
     return true;
 }
 
-// One traversal round (kdtree.cpp:250-330 as an explicit stack): descend to the
-// next leaf, test it, pop.  Returns the lane's new state: unchanged while the
-// query continues, else its result (a closest hit leaves {bx, by, tri} in d:
-// the direction is dead by then).
-//   Stack: entries {far node, tmax at push}; the top R live in an LDS ring
-//   [slot][thread] (blockDim.x threads), deeper ones spill to gstk
-//   [depth][gstride].  On pop the interval is [current tmax, entry.tmax]: the
-//   current tmax equals the push-time tsplit (DESIGN.md §4, stack invariant).
+// Measured and dropped forms of the round (trav_round, below):
 // (A wave-level mailbox -- per wave in LDS, the lanes for which a triangle was
 // a geometric miss in their current query, so a uniform leaf skips it when all
 // active lanes know it -- is exact too and measured 3% slower: the LDS lookup
@@ -173,7 +103,7 @@ __device__ __forceinline__ float4 sload_box(const float4 *p) {
     asm volatile("s_load_dwordx4 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(r) : "s"(p));
     return make_float4(r[0], r[1], r[2], r[3]);
 }
-// A fat record and its subtree box (CULL >= 2) under one scalar-load wait.
+// A fat record and its subtree box (camera cull) under one scalar-load wait.
 __device__ __forceinline__ void sload_fat_box(const uint4 *p, const float4 *q, uint4 &a, uint4 &b, float4 &box) {
     cr_v8u r;
     cr_v4f x;
@@ -222,10 +152,12 @@ __device__ __forceinline__ void sload_lcullc(const uint4 *p, uint32_t (&w)[12]) 
     for (int i = 0; i < 4; i++) w[8 + i] = b[i];
 }
 // The references of the leaf at `node` that the lane's ray (o, d: unit, segment [0, tmax]) must test
-// (leafcull.hpp); bits < count.  FORM 2: packed fixed-pad records (S.lcullp), 4: compressed (S.lcullc).
-template <bool SC, int FORM>
+// (leafcull.hpp); bits < count.  LC (the build's C::LC) 4: packed fixed-pad records (S.lcullp), 5: compressed
+// (S.lcullc).
+constexpr uint32_t lc_rec_bytes(int LC) { return 16u * (LC == 5 ? LC_RECC : LC_RECP); }
+template <bool SC, int LC>
 __device__ __forceinline__ uint32_t leaf_mask(const DevScene &S, uint32_t node, uint32_t count, f3 o, f3 d, float tmax) {
-    if (FORM == 4) {
+    if (LC == 5) {
         uint32_t w[12];
         if (SC && wave_uniform(node)) {
             sload_lcullc(S.lcullc + (size_t)LC_RECC * __builtin_amdgcn_readfirstlane(node), w);
@@ -241,7 +173,7 @@ __device__ __forceinline__ uint32_t leaf_mask(const DevScene &S, uint32_t node, 
         const float inv[3] = {__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y), __builtin_amdgcn_rcpf(d.z)};
         return leaf_cull_mask_c(ov, dv, inv, lc_unit(d.x, d.y, d.z), tmax, w, count, S.lcg);
     }
-    static_assert(FORM == 2 || FORM == 4, "leaf cull record forms: 2 (packed) or 4 (compressed)");
+    static_assert(LC == 4 || LC == 5, "leaf cull record forms: 4 (packed) or 5 (compressed)");
     LcFloat4 rec[LC_REC];
     constexpr int NR = LC_RECP;
     const float4 *recs = S.lcullp;
@@ -254,15 +186,8 @@ __device__ __forceinline__ uint32_t leaf_mask(const DevScene &S, uint32_t node, 
             const float4 v = p[i];
             rec[i] = LcFloat4{v.x, v.y, v.z, v.w};
         }
-#ifdef CR_PAD_LC // address-path calibration only: CR_PAD_LC extra 16-B loads of the record's own lines
-        typedef const __attribute__((address_space(1))) cr_v4f g_f4;
-        g_f4 *q = (g_f4 *)p;
-        asm volatile("" : "+v"(q));
-#pragma unroll
-        for (int i = 0; i < CR_PAD_LC; i++) {
-            const cr_v4f v = q[i];
-            asm volatile("" ::"v"(v));
-        }
+#ifdef CR_PAD_LC
+        pad_loads<CR_PAD_LC, -1>(p);
 #endif
     }
     const float ov[3] = {o.x, o.y, o.z}, dv[3] = {d.x, d.y, d.z};
@@ -293,15 +218,8 @@ template <bool SC> __device__ __forceinline__ void load_fat(const DevScene &S, u
     const uint4 *p = (const uint4 *)((const char *)S.fat + node * 32u);
     a = p[0];
     b = p[1];
-#ifdef CR_PAD_FETCH // address-path calibration only: CR_PAD_FETCH extra 16-B loads of the record's line
-    typedef const __attribute__((address_space(1))) cr_v4u g_u4;
-    g_u4 *q = (g_u4 *)p;
-    asm volatile("" : "+v"(q));
-#pragma unroll
-    for (int i = 0; i < CR_PAD_FETCH; i++) {
-        const cr_v4u v = q[i & 1];
-        asm volatile("" ::"v"(v));
-    }
+#ifdef CR_PAD_FETCH
+    pad_loads<CR_PAD_FETCH, 1>(p);
 #endif
 }
 
@@ -333,7 +251,6 @@ struct LeafX {
 };
 
 // The stack's top entry becomes the query's node and interval (stack invariant).
-// ring: the LDS ring's column of the wave's lane 0 ([slot][blockDim.x]); gstk as gstack_at's.
 // ring: the LDS ring [slot][blockDim.x]; gstk / gid: the stack-overflow area and the lane's global index.
 template <int R>
 __device__ __forceinline__ void trav_pop(uint2 *ring, uint2 *gstk, uint32_t gstride, uint32_t gid, Trav &T,
@@ -345,13 +262,101 @@ __device__ __forceinline__ void trav_pop(uint2 *ring, uint2 *gstk, uint32_t gstr
         T.nl--;
     } else {
         e = gstack_at(gstk, T.sp, gstride, gid);
-        if (pc) pc->vb += 8;
+        pc_load(pc, false, 8);
     }
     T.node = e.x;
     T.tmin = T.tmax; // == the popped entry's split distance (stack invariant)
     T.tmax = __uint_as_float(e.y);
 }
 
+// One kd decision at inner node nd (kdtree.cpp:258-275): T.node = the child to descend into (child + k,
+// k returned), the far child pushed when both are crossed, the ring's oldest entry spilled when it is full.
+// Reads C::FD (the split division) and C::BF (the decision as selects, a branch only around the push).
+// (o, d by reference and bdim = blockDim.x, tid = threadIdx.x read once by trav_round, as its lambdas hold
+// them: by value, or read here, kernels came out changed -- DESIGN.md §3.24.)
+template <class C>
+__device__ __forceinline__ uint32_t kd_step(uint2 nd, uint2 *ring, uint32_t bdim, uint32_t tid, uint2 *gstk, uint32_t gstride,
+                                            uint32_t gid, const f3 &o, const f3 &d, Trav &T, const Probe<C> &P) {
+    constexpr int R = C::R;
+    P.step(T.node, nd.x);
+    const uint32_t a = nd.y & 3u;
+    const float split = __uint_as_float(nd.x);
+    const float oa = comp(o, a), da = comp(d, a);
+    const float tsplit = C::FD ? div_by_rcp_wave(split - oa, da, comp(T.r, a)) : split_distance(split, oa, da);
+    const uint32_t below = (oa < split) || (oa == split && da <= 0);
+    const uint32_t child = nd.y >> 2;
+    uint32_t k;
+    if (C::BF) { // (bitwise logic on the lane masks: no short-circuit exec branches)
+        const bool near_only = (tsplit >= T.tmax) | (tsplit < 0);
+        const bool far_only = !near_only & (tsplit <= T.tmin);
+        const bool push = !near_only & !far_only;
+        k = far_only ? below : 1u - below;
+        if (push) {
+            const uint32_t slot = (T.sp & (R - 1)) * bdim + tid;
+            if (T.nl == R) P.load(false, 8);
+            if (T.nl == R) gstack_at(gstk, T.sp - R, gstride, gid) = ring[slot]; // spill the oldest
+            ring[slot] = make_uint2(child + below, __float_as_uint(T.tmax));
+        }
+        T.nl = push && T.nl < R ? T.nl + 1 : T.nl;
+        T.sp += push ? 1u : 0u;
+        T.tmax = push ? tsplit : T.tmax;
+    } else if (tsplit >= T.tmax || tsplit < 0) {
+        k = 1u - below;
+    } else if (tsplit <= T.tmin) {
+        k = below;
+    } else {
+        const uint2 e = make_uint2(child + below, __float_as_uint(T.tmax));
+        const uint32_t slot = (T.sp & (R - 1)) * bdim + tid;
+        if (T.nl == R) gstack_at(gstk, T.sp - R, gstride, gid) = ring[slot]; // spill the oldest
+        else T.nl++;
+        ring[slot] = e;
+        T.sp++;
+        T.tmax = tsplit;
+        k = 1u - below;
+    }
+    T.node = child + k;
+    return k;
+}
+
+// One triangle of the lane's leaf (kdtree.cpp:235-246 / 309-320); false: stop the leaf.  An accepted hit
+// goes to found / tri / bx / by and T.tmax, an occluder (shadow) to occluded.  (Everything by reference, the
+// scalars shadow and exclude too, as trav_round's lambda held them: by value the default kernels change.)
+template <class C>
+__device__ __forceinline__ bool tri_one(const f3 &o, const f3 &d, const bool &shadow, const uint32_t &exclude, const TriRec &r,
+                                        Trav &T, bool &found, bool &occluded, uint32_t &tri, float &bx, float &by,
+                                        const Probe<C> &P) {
+    const uint32_t id = rec_id(r);
+    if (shadow && id == exclude) return true;
+    P.test(true);
+    P.miss_census(o, d, r, id);
+    float ux, uy, t;
+    // BF: the lanes that failed an early test compute on (wave-uniform exits, no exec bookkeeping)
+    if (C::BF ? tri_test_wave(o, d, r, T.tmax, ux, uy, t) : tri_test(o, d, r, T.tmax, ux, uy, t)) {
+        if (shadow) {
+            occluded = true;
+            return false;
+        }
+        bx = ux;
+        by = uy;
+        T.tmax = t;
+        tri = id;
+        found = true;
+    }
+    return true;
+}
+
+// One traversal round (kdtree.cpp:250-330 as an explicit stack): descend to the next leaf, test it, pop.
+// Returns the lane's new state: unchanged while the query continues, else its result (a closest hit leaves
+// {bx, by, tri} in d: the direction is dead by then), or ST_LEAFX with the leaf's masked references in *lx
+// (LX builds: wf_trace runs leaf_exchange with the whole wave and ends the round itself).
+//   Stack: entries {far node, tmax at push}; the top R live in the LDS ring [slot][blockDim.x] (ring),
+//   deeper ones spill to gstk [depth][gstride].  On pop the interval is [current tmax, entry.tmax]: the
+//   current tmax equals the push-time tsplit (DESIGN.md §4, stack invariant).
+// The body's stages in order -- the descent (kd_step per decision; C::FAT: two levels per fetch), the
+// leaf's references (camera cull box, leaf cull mask), one leaf tester by the build and the leaf, the
+// round's end -- with the C:: knobs each reads and the builds that reach it: DESIGN.md §3.24, which also
+// records why the descent loop and the testers stay blocks of this function (csx, csy, cull, cull_node:
+// camera cull only; lx: LX only; c, dg, pc: the probe's).
 template <class C>
 __device__ __forceinline__ uint32_t trav_round(int lc_debug, uint32_t lc_min, const DevScene &S, uint2 *ring, uint2 *gstk, uint32_t gstride,
                                                uint32_t gid, f3 o, f3 &d, bool shadow, uint32_t exclude, Trav &T,
@@ -359,7 +364,7 @@ __device__ __forceinline__ uint32_t trav_round(int lc_debug, uint32_t lc_min, co
                                                const float4 *cull_node = nullptr, Diag *dg = nullptr,
                                                Pc *pc = nullptr, uint32_t quorum = 0, LeafX *lx = nullptr) {
     static constexpr int R = C::R, CULL = C::CULL, LC = C::LC;
-    static constexpr bool FULL = C::FULL, FD = C::FD, SC = C::SC, FAT = C::FAT, BF = C::BF;
+    static constexpr bool FULL = C::FULL, SC = C::SC, FAT = C::FAT, BF = C::BF;
     // quorum (lean FAT builds without the camera cull): the wave's descent stops at a fetch once at most
     // quorum / 64 of the lanes that entered the round still descend; those keep T.node (the node to fetch)
     // and their interval and go on next round -- the same node visits with the same intervals, so the
@@ -367,82 +372,26 @@ __device__ __forceinline__ uint32_t trav_round(int lc_debug, uint32_t lc_min, co
     const uint32_t nbusy = quorum ? (uint32_t)__popcll(__ballot(1)) : 0u;
     constexpr uint32_t PENDING_LEAF = 0xfffffffeu;
     bool pending = false;
-    if (pc && wave_leader()) pc->waves++;
-    // performed-work accounting of record loads (pc: perf builds)
+    const Probe<C> P = {c, dg, pc};
+    P.round();
     auto lrec = [&](uint32_t i) -> TriRec {
-        if (pc) pc->vb += 16u * REC_STRIDE;
+        P.load(false, 16u * REC_STRIDE);
         return load_rec(S, i);
     };
     auto srec = [&](const float4 *q) -> TriRec {
-        pc_load(pc, true, 16u * REC_STRIDE);
+        P.load(true, 16u * REC_STRIDE);
         return sload_rec(q);
     };
-    static_assert(!CULL || (BF && SC && !FULL), "cull: lean BF + SC builds");
-    static_assert(CULL < 2 || FAT, "subtree cull: fat-record builds");
+    static_assert(CULL == 0 || CULL == 2, "camera cull: none, or references, leaves and subtrees");
+    static_assert(!CULL || (FAT && BF && SC && !FULL), "cull: lean fat-record BF + SC builds");
     static_assert(!LC || ((LC == 4 || LC == 5) && !CULL && BF && SC && !FULL), "leaf cull: lean BF + SC builds, forms 4 / 5");
     static_assert(!C::LX || LC, "leaf exchange: leaf-cull builds");
+    // (read once, here, and handed to kd_step: reading them at the push, or not at all, moves the registers
+    // of 44 kernels -- DESIGN.md §3.24)
     const uint32_t bdim = blockDim.x, tid = threadIdx.x;
-    // one kd decision at inner node nd (kdtree.cpp:258-275): T.node = the child to
-    // descend into (child + k), the far child pushed when both are crossed
-    auto step = [&](uint2 nd) -> uint32_t {
-        if (pc) pc->steps++;
-#ifdef CR_PAD_STEP // issue-cost calibration only: CR_PAD_STEP extra VALU per shadow descent step
-        if (C::SHADOW) {
-            uint32_t z = nd.x;
-#pragma unroll
-            for (int i = 0; i < CR_PAD_STEP; i++) asm volatile("v_mov_b32 %0, %0" : "+v"(z));
-        }
-#endif
-        if (FULL) {
-            c.inner++;
-            const bool uni = wave_uniform(T.node);
-            const uint32_t lines = wave_distinct(T.node >> (FAT ? 2 : 4)); // 32-B / 8-B node records
-            if (wave_leader()) {
-                c.wave_desc++;
-                c.wave_desc_uniform += uni;
-                c.wave_desc_lines += lines;
-            }
-        }
-        const uint32_t a = nd.y & 3u;
-        const float split = __uint_as_float(nd.x);
-        const float oa = comp(o, a), da = comp(d, a);
-        const float tsplit = FD ? div_by_rcp_wave(split - oa, da, comp(T.r, a)) : split_distance(split, oa, da);
-        const uint32_t below = (oa < split) || (oa == split && da <= 0);
-        const uint32_t child = nd.y >> 2;
-        uint32_t k;
-        if (BF) { // (bitwise logic on the lane masks: no short-circuit exec branches)
-            const bool near_only = (tsplit >= T.tmax) | (tsplit < 0);
-            const bool far_only = !near_only & (tsplit <= T.tmin);
-            const bool push = !near_only & !far_only;
-            k = far_only ? below : 1u - below;
-            if (push) {
-                const uint32_t slot = (T.sp & (R - 1)) * bdim + tid;
-                if (pc && T.nl == R) pc->vb += 8;
-                if (T.nl == R) gstack_at(gstk, T.sp - R, gstride, gid) = ring[slot]; // spill the oldest
-                ring[slot] = make_uint2(child + below, __float_as_uint(T.tmax));
-            }
-            T.nl = push && T.nl < R ? T.nl + 1 : T.nl;
-            T.sp += push ? 1u : 0u;
-            T.tmax = push ? tsplit : T.tmax;
-        } else if (tsplit >= T.tmax || tsplit < 0) {
-            k = 1u - below;
-        } else if (tsplit <= T.tmin) {
-            k = below;
-        } else {
-            const uint2 e = make_uint2(child + below, __float_as_uint(T.tmax));
-            const uint32_t slot = (T.sp & (R - 1)) * bdim + tid;
-            if (T.nl == R) gstack_at(gstk, T.sp - R, gstride, gid) = ring[slot]; // spill the oldest
-            else T.nl++;
-            ring[slot] = e;
-            T.sp++;
-            T.tmax = tsplit;
-            k = 1u - below;
-        }
-        T.node = child + k;
-        return k;
-    };
+    auto step = [&](uint2 nd) -> uint32_t { return kd_step<C>(nd, ring, bdim, tid, gstk, gstride, gid, o, d, T, P); };
     uint2 nd;
-    // CULL >= 2: a fetched node whose subtree box excludes the sample is treated as an
+    // CULL: a fetched node whose subtree box excludes the sample is treated as an
     // empty leaf -- none of its triangles can accept, so the traversal would leave it
     // without a hit and with tmax = its interval's end, which is exactly this state
     bool culled = false;
@@ -452,9 +401,9 @@ __device__ __forceinline__ uint32_t trav_round(int lc_debug, uint32_t lc_min, co
     if (FAT) { // two levels per dependent load: a node's record carries its children's
         uint4 f0, f1;
         auto fetch = [&](uint32_t node) {
-            if (CULL >= 2) { // the record and the subtree box, loads issued together
+            if (CULL) { // the record and the subtree box, loads issued together
                 float4 b;
-                pc_load(pc, SC && wave_uniform(node), 48);
+                P.load(SC && wave_uniform(node), 48);
                 if (SC && wave_uniform(node)) {
                     const uint32_t un = __builtin_amdgcn_readfirstlane(node);
                     sload_fat_box(S.fat + 2u * un, cull_node + un, f0, f1, b);
@@ -469,18 +418,10 @@ __device__ __forceinline__ uint32_t trav_round(int lc_debug, uint32_t lc_min, co
                     culled = true;
                     nd = make_uint2(0xffffffffu, 3u); // an empty leaf no real leaf shares `first` with
                 }
-                return;
             } else {
-                pc_load(pc, SC && wave_uniform(node), 32);
+                P.load(SC && wave_uniform(node), 32);
                 load_fat<SC>(S, node, f0, f1);
-            }
-            nd = make_uint2(f0.x, f0.y);
-            if (CULL >= 2) {
-                const float4 b = load_box<SC>(cull_node, node);
-                if (!(csx >= b.x && csx <= b.y && csy >= b.z && csy <= b.w)) {
-                    culled = true;
-                    nd = make_uint2(0xffffffffu, 3u); // an empty leaf no real leaf shares `first` with
-                }
+                nd = make_uint2(f0.x, f0.y);
             }
         };
         fetch(T.node);
@@ -500,142 +441,53 @@ __device__ __forceinline__ uint32_t trav_round(int lc_debug, uint32_t lc_min, co
         }
         pending = !FULL && !CULL && quorum && nd.x == PENDING_LEAF;
     } else {
-        pc_load(pc, SC && wave_uniform(T.node), 8);
+        P.load(SC && wave_uniform(T.node), 8);
         nd = load_node<SC>(S, T.node);
         while ((nd.y & 3u) != 3u) {
             step(nd);
-            pc_load(pc, SC && wave_uniform(T.node), 8);
+            P.load(SC && wave_uniform(T.node), 8);
             nd = load_node<SC>(S, T.node);
         }
     }
     if (pending) return shadow ? ST_SHADOW : ST_CLOSEST; // descends on next round from T.node
-    if (FULL) {
-        c.leaf++;
-        if (wave_leader()) c.wave_round++;
-    }
-    if (pc) pc->leaves++;
+    P.leaf();
     first = nd.x;
     count = nd.y >> 2;
     lin = !culled; // CULL: the sample lies in the leaf's box (the union of its references')
     if (CULL && !culled) {
-        pc_load(pc, SC && wave_uniform(T.node), 16);
+        P.load(SC && wave_uniform(T.node), 16);
         const float4 lb = load_box<SC>(cull_node, T.node);
         lin = csx >= lb.x && csx <= lb.y && csy >= lb.z && csy <= lb.w;
     }
     // LC: the references to test (bit j: first + j); count > LC_MAXREFS: every one (lmask unused)
     lmask = 0u;
-    if (LC && count && count <= (uint32_t)LC_MAXREFS) {
-        // leaves below lc_min: every reference, no check
-        const uint32_t lcid = T.node;
-        if (pc && count >= lc_min) {
-            pc->masks++;
-            pc_load(pc, SC && wave_uniform(lcid), 16u * (LC == 5 ? LC_RECC : LC_RECP));
+    if constexpr (LC != 0) { // (leaf_mask has no form for LC 0)
+        if (count && count <= (uint32_t)LC_MAXREFS) {
+            // leaves below lc_min: every reference, no check
+            const uint32_t lcid = T.node;
+            if (count >= lc_min) P.mask(SC && wave_uniform(lcid), lc_rec_bytes(LC));
+            lmask = count >= lc_min ? leaf_mask<SC, LC>(S, lcid, count, o, d, T.tmax)
+                                    : (count >= 32 ? 0xffffffffu : (1u << count) - 1u);
+            if (lc_debug) lmask = lc_debug == 1 ? (count >= 32 ? 0xffffffffu : (1u << count) - 1u) : 0u;
         }
-        lmask = count >= lc_min ? leaf_mask<SC, LC == 5 ? 4 : 2>(S, lcid, count, o, d, T.tmax)
-                                : (count >= 32 ? 0xffffffffu : (1u << count) - 1u);
-        if (lc_debug) lmask = lc_debug == 1 ? (count >= 32 ? 0xffffffffu : (1u << count) - 1u) : 0u;
     }
     bool found = false, occluded = false;
     uint32_t tri = 0;
     float bx = 0.f, by = 0.f;
-    // one triangle of the leaf (kdtree.cpp:235-246 / 309-320); false: stop the leaf
     auto test = [&](const TriRec &r) -> bool {
-        const uint32_t id = rec_id(r);
-        if (shadow && id == exclude) return true;
-        if (FULL) c.tritest++;
-        if (pc) pc->tests++;
-        if (FULL && dg && dg->on) { // repeated-miss census: a miss for any segment is one for every later one
-            dg->v[DIAG_TESTS]++;
-            float gx, gy, gt;
-            if (!tri_test(o, d, r, __builtin_inff(), gx, gy, gt)) {
-                dg->v[DIAG_GEOMISS]++;
-                const uint32_t n = dg->n;
-                bool r1 = false, r4 = false, r8 = false;
-#pragma unroll
-                for (uint32_t j = 0; j < 8; j++) {
-                    const bool m = j < n && dg->mb[(n - 1 - j) & 7u] == id;
-                    r1 = r1 | (m & (j < 1));
-                    r4 = r4 | (m & (j < 4));
-                    r8 = r8 | m;
-                }
-                dg->v[DIAG_REP1] += r1;
-                dg->v[DIAG_REP4] += r4;
-                dg->v[DIAG_REP8] += r8;
-                dg->mb[n & 7u] = id;
-                dg->n = n + 1;
-            }
-        }
-        float ux, uy, t;
-        // BF: the lanes that failed an early test compute on (wave-uniform exits, no exec bookkeeping)
-        if (BF ? tri_test_wave(o, d, r, T.tmax, ux, uy, t) : tri_test(o, d, r, T.tmax, ux, uy, t)) {
-            if (shadow) {
-                occluded = true;
-                return false;
-            }
-            bx = ux;
-            by = uy;
-            T.tmax = t;
-            tri = id;
-            found = true;
-        }
-        return true;
+        return tri_one<C>(o, d, shadow, exclude, r, T, found, occluded, tri, bx, by, P);
     };
-    auto tally_tri = [&](uint32_t ref) {
-        if (FULL) {
-            const bool uni = wave_uniform(ref);
-            const uint32_t lines = wave_distinct(ref * (16u * REC_STRIDE) >> 7);
-            if (wave_leader()) {
-                c.wave_tri++;
-                c.wave_tri_uniform += uni;
-                c.wave_tri_lines += lines;
-            }
-        }
-    };
-    if (FULL && (!dg || dg->on) && !wave_uniform(first)) { // what staging the wave's leaves in LDS would take
-        uint64_t m = __ballot(count > 0);
-        uint32_t nd = 0, nr = 0, mc = 0, lt = 0;
-        const uint32_t lanes = (uint32_t)__popcll(m);
-        while (m) {
-            const int l = __ffsll((long long)m) - 1;
-            const uint32_t f = (uint32_t)__shfl((int)first, l, 64), n = (uint32_t)__shfl((int)count, l, 64);
-            const uint64_t same = __ballot(first == f && count > 0);
-            m &= ~same;
-            nd++;
-            nr += n;
-            mc = max(mc, n);
-            lt += n * (uint32_t)__popcll(same);
-        }
-        if (wave_leader()) {
-            c.leaf_rounds++;
-            c.leaf_distinct += nd;
-            c.leaf_records += nr;
-            c.leaf_fit21 += nr <= 21;
-            c.leaf_fit56 += nr <= 56;
-            if (dg) {
-                dg->v[DIAG_ROUNDS]++;
-                dg->v[DIAG_LANES] += lanes;
-                dg->v[DIAG_DISTINCT] += nd;
-                dg->v[DIAG_RECORDS] += nr;
-                dg->v[DIAG_MAXCOUNT] += mc;
-                dg->v[DIAG_LANETESTS] += lt;
-                dg->v[DIAG_FIT64] += nr <= 64;
-                dg->v[DIAG_FIT128] += nr <= 128;
-            }
-        }
-    } else if (FULL && dg && dg->on && wave_leader()) {
-        dg->v[DIAG_UROUNDS]++;
-    }
+    P.leaf_census(first, count);
     if (BF && SC && wave_uniform(first)) { // uniform leaf, results by select
         const uint32_t uf = __builtin_amdgcn_readfirstlane(first), uc = __builtin_amdgcn_readfirstlane(count);
         const float4 *base = S.recs + (size_t)REC_STRIDE * uf;
         // one triangle of the uniform leaf; false: every active lane occluded (stop)
         // in: the lane tests this triangle (LC: the bit of its own mask)
         auto utest = [&](const TriRec &r, uint32_t j, bool in = true) -> bool {
-            tally_tri(uf + j);
+            P.tri_lines(uf + j);
             const uint32_t id = rec_id(r);
             const bool live = in & !(shadow & (occluded | (id == exclude)));
-            if (FULL) c.tritest += live ? 1u : 0u;
-            if (pc) pc->tests += live ? 1u : 0u;
+            P.test(live);
             float ux, uy, t;
             const bool acc = live & tri_test_wave(o, d, r, T.tmax, ux, uy, t);
             if (shadow) {
@@ -652,7 +504,7 @@ __device__ __forceinline__ uint32_t trav_round(int lc_debug, uint32_t lc_min, co
         if (CULL) {
             const float4 *cb = cull + uf;
             for (uint32_t j = 0; j < uc && __ballot(lin); j += 4) {
-                pc_load(pc, true, 64);
+                P.load(true, 64);
                 const cr_v16f bx = sload_box4(cb + j);
 #pragma unroll
                 for (uint32_t k = 0; k < 4; k++) {
@@ -678,7 +530,7 @@ __device__ __forceinline__ uint32_t trav_round(int lc_debug, uint32_t lc_min, co
     } else if (SC && wave_uniform(first)) { // every lane at the same leaf: scalar loads
         const float4 *base = S.recs + (size_t)REC_STRIDE * __builtin_amdgcn_readfirstlane(first);
         for (uint32_t j = 0; j < count; j++) {
-            tally_tri(first + j);
+            P.tri_lines(first + j);
             if (!test(srec(base + (size_t)REC_STRIDE * j))) break;
         }
     } else if (C::LX && LC && count <= (uint32_t)LC_MAXREFS) { // tests deferred to the wave's leaf exchange
@@ -689,18 +541,7 @@ __device__ __forceinline__ uint32_t trav_round(int lc_debug, uint32_t lc_min, co
         }
     } else if (LC && count <= (uint32_t)LC_MAXREFS) { // the mask's references, pipelined one ahead
         uint32_t m = lmask;
-        if (pc) { // the divergent leaf loop's shape: iterations = the largest lane mask
-            const uint32_t pop = (uint32_t)__builtin_popcount(m);
-            const uint32_t lanes = (uint32_t)__popcll(__ballot(pop > 0));
-            uint32_t mx = 0;
-            while (__ballot(pop > mx)) mx++;
-            if (lanes && wave_leader()) {
-                pc->drounds++;
-                pc->diters += mx;
-                pc->dlanes += lanes;
-            }
-            pc->dtests += pop;
-        }
+        P.dloop(m);
         TriRec nx;
         if (m) nx = lrec(first + (uint32_t)__builtin_ctz(m));
         while (m) {
@@ -713,11 +554,11 @@ __device__ __forceinline__ uint32_t trav_round(int lc_debug, uint32_t lc_min, co
         if (!lin) count = 0;
         float4 nb = make_float4(0.f, 0.f, 0.f, 0.f);
         if (count) nb = cull[first];
-        if (pc && count) pc->vb += 16;
+        if (count) P.load(false, 16);
         for (uint32_t j = 0; j < count; j++) {
             const float4 b = nb;
             if (j + 1 < count) nb = cull[first + j + 1];
-            if (pc && j + 1 < count) pc->vb += 16;
+            if (j + 1 < count) P.load(false, 16);
             if (csx >= b.x && csx <= b.y && csy >= b.z && csy <= b.w)
                 if (!test(lrec(first + j))) break;
         }
@@ -725,7 +566,7 @@ __device__ __forceinline__ uint32_t trav_round(int lc_debug, uint32_t lc_min, co
         TriRec nx;
         if (count) nx = lrec(first);
         for (uint32_t j = 0; j < count; j++) { // software pipeline: triangle j+1's loads before j's test
-            tally_tri(first + j);
+            P.tri_lines(first + j);
             const TriRec r = nx;
             if (j + 1 < count) nx = lrec(first + j + 1);
             if (!test(r)) break;

@@ -461,7 +461,9 @@ __global__ void __launch_bounds__(WF_TRACE_BLOCK, C::MINW) wf_trace(RenderArgs A
                 S, ring_lds, W.gstack, W.gstride, gid, o, d, SHADOW, exclude, T, c, csx, csy, CULL ? A.cull : nullptr,
                 CULL ? A.cull_node : nullptr, FULL ? &dg : nullptr, PC ? &pc : nullptr, A.desc_quorum, &lx);
         // LX: the deferred leaves' tests by the whole wave (traverse.hpp leaf_exchange), then each deferred
-        // lane ends its round as trav_round does after a leaf
+        // lane ends its round as trav_round does after a leaf.  leaf_exchange needs every lane of the wave
+        // active: that holds here and only here -- outside the `state == busy_st` branch, in a loop that lanes
+        // leave together (idle and ST_DONE lanes stay in it) -- so this is its one call site
         if (C::LX && __ballot(r == ST_LEAFX)) {
             __shared__ uint32_t lx_lds[WF_TRACE_WAVES][192]; // per wave of a block of WF_TRACE_BLOCK threads
             static_assert(sizeof(lx_lds) == WF_TRACE_BLOCK / 64 * 192 * sizeof(uint32_t), "one exchange area per wave");

@@ -21,9 +21,12 @@
 
 namespace cr {
 
-// A trace build's configuration: every knob of trav_round (traverse.hpp) and wf_trace (wavefront.hip),
-// named.  The defaults are the plain reference build; a build is a type deriving from this and restating
-// what it changes (namespace tc below), so a kernel reads e.g. wf_trace<cr::tc::ShadowFatLc5Fd>.
+// A trace build's configuration, every knob named.  Who reads which: R, FD, BF -- traverse.hpp kd_step;
+// FAT, CULL, SC and the quorum's FULL / CULL guard -- trav_round's descent; CULL, LC, FIX -- its leaf
+// references; BF, SC, LC, LX, CULL -- its choice of leaf tester; FULL, PC, SHADOW (pad) -- travprobe.hpp;
+// SHADOW, CAM, DEAD, FIX, LX, LXD, MINW -- wf_trace (wavefront.hip).  DESIGN.md §3.24 has the map by stage.
+// The defaults are the plain reference build; a build is a type deriving from this and restating what it
+// changes (namespace tc below), so a kernel reads e.g. wf_trace<cr::tc::ShadowFatLc5Fd>.
 struct TraceDefaults {
     static constexpr bool SHADOW = false; // shadow (any-hit) queries, else closest-hit
     static constexpr bool FULL = false;   // counting build: SURVEY §8d work counters and diagnostics

@@ -1,7 +1,9 @@
 """Register use, spills and LDS of the device kernels in a built object (gfx950 code-object notes).
     python scripts/kernel_regs.py [chiaroscuro-raytracer_amd/build/wavefront.o] [name-filter]
     python scripts/kernel_regs.py --diff A.o B.o     the two objects' device code kernel by kernel: the notes
-        (registers, spills, LDS, scratch, argument layout) and the instruction stream; exit 1 on any difference"""
+        (registers, spills, LDS, scratch, argument layout) and the instruction stream.  Every kernel is
+        identical, equivalent (same notes, the same instructions in another order) or changed (with the deltas
+        of registers, spills, scratch and instruction count); exit 1 on any difference"""
 import os
 import re
 import subprocess
@@ -60,22 +62,57 @@ def bodies(obj):
     return out
 
 
+def opcode(ins):
+    """An instruction's mnemonic; a label line (no operands, ends with ':') counts as itself."""
+    return ins.split(None, 1)[0] if ins else ins
+
+
+NOTE_KEYS = (("vgpr", "vgpr_count"), ("sgpr", "sgpr_count"), ("vspill", "vgpr_spill_count"),
+             ("sspill", "sgpr_spill_count"), ("scratch", "private_segment_fixed_size"))
+
+
+def classify(note_a, note_b, ins_a, ins_b):
+    """One kernel of two objects, from its notes (text) and instruction lists:
+    "identical"   same notes, same instruction stream;
+    "equivalent"  same notes, same instruction count, same multiset of opcodes (a reordering);
+    "changed"     anything else."""
+    if note_a != note_b or not ins_a or not ins_b:
+        return "changed"
+    if ins_a == ins_b:
+        return "identical"
+    if len(ins_a) == len(ins_b) and sorted(map(opcode, ins_a)) == sorted(map(opcode, ins_b)):
+        return "equivalent"
+    return "changed"
+
+
+def deltas(note_a, note_b, ins_a, ins_b):
+    """B - A of the register, spill and scratch notes and of the instruction count."""
+    get = lambda b, k: int((re.search(r"\." + k + r":\s+(\d+)", b) or [0, 0])[1])
+    out = {n: get(note_b, k) - get(note_a, k) for n, k in NOTE_KEYS}
+    out["instructions"] = len(ins_b or []) - len(ins_a or [])
+    return out
+
+
 def diff(a, b):
-    """Prints the comparison of two objects' device code; the number of kernels that differ or are missing."""
+    """Prints the comparison of two objects' device code, every kernel classified (classify); the number of
+    kernels that are not identical or are missing."""
     na, nb, ba, bb = note_blocks(a), note_blocks(b), bodies(a), bodies(b)
-    bad = 0
+    count = {"identical": 0, "equivalent": 0, "changed": 0, "missing": 0}
     for name in sorted(set(na) | set(nb)):
         if name not in na or name not in nb:
             print("only in %s: %s" % ("A" if name in na else "B", name))
-            bad += 1
-        elif na[name] != nb[name] or ba.get(name) != bb.get(name) or not ba.get(name):
-            what = [w for w, ne in (("notes", na[name] != nb[name]), ("instructions", ba.get(name) != bb.get(name))) if ne]
-            print("differs (%s): %s" % (", ".join(what) or "no body", name))
-            bad += 1
-    same = len(set(na) & set(nb)) - sum(1 for n in set(na) & set(nb)
-                                         if na[n] != nb[n] or ba.get(n) != bb.get(n) or not ba.get(n))
-    print("kernels A %d B %d, identical notes and instructions %d, different or missing %d" % (len(na), len(nb), same, bad))
-    return bad
+            count["missing"] += 1
+            continue
+        tier = classify(na[name], nb[name], ba.get(name), bb.get(name))
+        count[tier] += 1
+        if tier == "equivalent":
+            print("equivalent: %s" % name)
+        elif tier == "changed":
+            d = deltas(na[name], nb[name], ba.get(name), bb.get(name))
+            print("changed (%s): %s" % (" ".join("%s %+d" % kv for kv in d.items()), name))
+    print("kernels A %d B %d, identical %d, equivalent %d, changed %d, missing %d" % (
+        len(na), len(nb), count["identical"], count["equivalent"], count["changed"], count["missing"]))
+    return count["equivalent"] + count["changed"] + count["missing"]
 
 
 if __name__ == "__main__":
