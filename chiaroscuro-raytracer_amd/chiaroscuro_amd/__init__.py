@@ -201,6 +201,23 @@ class CrAdaptiveStats(C.Structure):
                 "layers": int(self.layers), "checks": int(self.checks), "max_err": float(self.max_err)}
 
 
+class CrDenoiseParams(C.Structure):
+    """cr_denoise_params (include/chiaro_hip.h "guide buffers and denoiser")."""
+    _fields_ = [("levels", C.c_uint32), ("sigma_l", C.c_float), ("sigma_z", C.c_float), ("sigma_a", C.c_float),
+                ("normal_squarings", C.c_uint32)]
+
+
+def denoise_params(levels=None, sigma_l=None, sigma_z=None, sigma_a=None, normal_squarings=None) -> CrDenoiseParams:
+    """cr_denoise_params_default (4, 4.0, 0.1, 0.1, 5) with the given fields replaced."""
+    dp = CrDenoiseParams()
+    libs()[0].cr_denoise_params_default(C.byref(dp))
+    for k, v in (("levels", levels), ("sigma_l", sigma_l), ("sigma_z", sigma_z), ("sigma_a", sigma_a),
+                 ("normal_squarings", normal_squarings)):
+        if v is not None:
+            setattr(dp, k, v)
+    return dp
+
+
 def tonemap_params(exposure, defog=0.0, knee_low=0.0, knee_high=5.0, gamma=2.2) -> CrTonemapParams:
     """cr_tonemap_setup: normalizeImage's host scalars (src/rayTracer.cpp:196-205)."""
     t = CrTonemapParams()
@@ -227,7 +244,9 @@ HIP_SYMBOLS = ("cr_create", "cr_destroy", "cr_last_error", "cr_upload_scene", "c
                "cr_noise_struct_sizes", "cr_render_layers_noise_device", "cr_noise_device", "cr_render_layers_noise",
                "cr_noise", "cr_set_noise_accumulator", "cr_render_until",
                "cr_adaptive_struct_sizes", "cr_render_layers_list_device", "cr_noise_select_device",
-               "cr_render_adaptive")
+               "cr_render_adaptive",
+               "cr_denoise_params_default", "cr_denoise_struct_sizes", "cr_guides_device", "cr_guides",
+               "cr_denoise_device", "cr_denoise")
 HOST_SYMBOLS = ("chiaro_last_error", "chiaro_scene_create", "chiaro_scene_info_get", "chiaro_scene_destroy",
                 "chiaro_model_create", "chiaro_model_load", "chiaro_model_num_meshes", "chiaro_model_num_triangles",
                 "chiaro_model_num_textures", "chiaro_model_triangles", "chiaro_model_texture",
@@ -245,7 +264,8 @@ HOST_SYMBOLS = ("chiaro_last_error", "chiaro_scene_create", "chiaro_scene_info_g
                 "chiaro_preview_texture", "chiaro_preview_state", "chiaro_preview_destroy",
                 "chiaro_preview_camera_replay", "chiaro_raytracer_raytrace_until", "chiaro_raytracer_noise",
                 "chiaro_raytracer_noise_map", "chiaro_noise_struct_sizes", "chiaro_raytracer_raytrace_adaptive",
-                "chiaro_raytracer_adaptive", "chiaro_raytracer_layer_map")
+                "chiaro_raytracer_adaptive", "chiaro_raytracer_layer_map", "chiaro_raytracer_denoise",
+                "chiaro_raytracer_denoised")
 
 P = C.c_void_p
 FP = C.POINTER(C.c_float)
@@ -363,6 +383,15 @@ def libs():
     _sig(hip, "cr_render_adaptive", C.c_int,
          [CTX, C.POINTER(CrCamera), C.POINTER(CrRenderParams), C.POINTER(CrAdaptiveParams), NP, FP, FP, UP,
           C.POINTER(CrAdaptiveStats)])
+    DP = C.POINTER(CrDenoiseParams)
+    _sig(hip, "cr_denoise_params_default", None, [DP])
+    _sig(hip, "cr_denoise_struct_sizes", None, [UP])
+    _sig(hip, "cr_guides_device", C.c_int, [CTX, C.POINTER(CrCamera), C.c_uint32, C.c_uint32, P, P, P, P])
+    _sig(hip, "cr_guides", C.c_int, [CTX, C.POINTER(CrCamera), C.c_uint32, C.c_uint32, FP, FP, FP])
+    _sig(hip, "cr_denoise_device", C.c_int,
+         [CTX, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, DP, P, P, P, P, P, P, P, P, P])
+    _sig(hip, "cr_denoise", C.c_int,
+         [CTX, C.POINTER(CrCamera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, DP, UP, FP, FP])
 
     _sig(host, "chiaro_last_error", C.c_char_p, [])
     _sig(host, "chiaro_scene_create", P, [C.c_int, C.POINTER(C.c_char_p)])
@@ -396,6 +425,8 @@ def libs():
                                                                C.POINTER(C.c_uint64)])
     _sig(host, "chiaro_raytracer_adaptive", C.c_int, [P, C.POINTER(CrAdaptiveStats)])
     _sig(host, "chiaro_raytracer_layer_map", C.c_int, [P, UP])
+    _sig(host, "chiaro_raytracer_denoise", C.c_int, [P, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_uint32])
+    _sig(host, "chiaro_raytracer_denoised", FP, [P])
     _sig(host, "chiaro_raytracer_pixels", FP, [P])
     _sig(host, "chiaro_raytracer_data", C.POINTER(C.c_uint8), [P])
     _sig(host, "chiaro_raytracer_maxval", C.c_float, [P])
@@ -706,6 +737,50 @@ class Device:
                                                _ptr(mom) if want_m2 else None, _ptr(lmap, C.c_uint32), C.byref(st)),
                   "cr_render_adaptive")
         return out, mom, lmap, st.as_dict()
+
+    def guides_device(self, cam: CrCamera, xres: int, yres: int, d_albedo_ptr: int = 0, d_normal_ptr: int = 0,
+                      d_depth_ptr: int = 0, stream: int = 0):
+        """cr_guides_device: the first hit's albedo and normal [yres][xres][3] and depth [yres][xres] (a miss:
+        zeros and -1) of one ray through each pixel centre, into the device arrays that are not 0, enqueued on
+        `stream` without a host synchronisation."""
+        self._chk(libs()[0].cr_guides_device(self._c, C.byref(cam), int(xres), int(yres),
+                                             C.c_void_p(d_albedo_ptr or None), C.c_void_p(d_normal_ptr or None),
+                                             C.c_void_p(d_depth_ptr or None), C.c_void_p(stream)), "cr_guides_device")
+
+    def guides(self, cam: CrCamera, xres: int, yres: int, want=("albedo", "normal", "depth")) -> dict:
+        """cr_guides: {"albedo", "normal" [yres][xres][3], "depth" [yres][xres]} of the names in `want`."""
+        out = {k: np.zeros((yres, xres) + ((3,) if k != "depth" else ()), np.float32) for k in want}
+        ptr = lambda k: _ptr(out[k]) if k in out else None
+        self._chk(libs()[0].cr_guides(self._c, C.byref(cam), int(xres), int(yres), ptr("albedo"), ptr("normal"),
+                                      ptr("depth")), "cr_guides")
+        return out
+
+    def denoise_device(self, xres: int, yres: int, layers: int, spp: int, dp: CrDenoiseParams, d_frame_ptr: int,
+                       d_m2_ptr: int, d_layer_map_ptr: int, d_albedo_ptr: int, d_normal_ptr: int, d_depth_ptr: int,
+                       d_out_ptr: int, d_var_out_ptr: int = 0, stream: int = 0):
+        """cr_denoise_device: the variance-guided a-trous filter of a device frame, moment frame and guides into
+        d_out [yres][xres][3] (and the filtered variance into d_var_out [yres][xres] when given); d_layer_map_ptr
+        (uint32 [yres][xres], an adaptive frame's layer counts) may be 0.  Enqueued on `stream`."""
+        self._chk(libs()[0].cr_denoise_device(self._c, int(xres), int(yres), int(layers), int(spp), C.byref(dp),
+                                              C.c_void_p(d_frame_ptr), C.c_void_p(d_m2_ptr),
+                                              C.c_void_p(d_layer_map_ptr or None), C.c_void_p(d_albedo_ptr),
+                                              C.c_void_p(d_normal_ptr), C.c_void_p(d_depth_ptr),
+                                              C.c_void_p(d_out_ptr), C.c_void_p(d_var_out_ptr or None),
+                                              C.c_void_p(stream)), "cr_denoise_device")
+
+    def denoise(self, cam: CrCamera, xres: int, yres: int, layers: int, spp: int, dp: CrDenoiseParams | None = None,
+                layer_map: np.ndarray | None = None, want_var: bool = True):
+        """cr_denoise on the ctx's two accumulators (left as they are), the guides computed here; returns
+        (frame [yres][xres][3], variance [yres][xres] or None)."""
+        dp = dp if dp is not None else denoise_params()
+        out = np.zeros((yres, xres, 3), np.float32)
+        var = np.zeros((yres, xres), np.float32) if want_var else None
+        lm = None if layer_map is None else np.ascontiguousarray(layer_map, np.uint32)
+        assert lm is None or lm.size == xres * yres
+        self._chk(libs()[0].cr_denoise(self._c, C.byref(cam), int(xres), int(yres), int(layers), int(spp), C.byref(dp),
+                                       None if lm is None else _ptr(lm, C.c_uint32), _ptr(out),
+                                       _ptr(var) if want_var else None), "cr_denoise")
+        return out, var
 
     def render_device(self, cam, p, d_frame_ptr: int, stream: int = 0):
         self._chk(libs()[0].cr_render_device(self._c, C.byref(cam), C.byref(p), C.c_void_p(d_frame_ptr),
@@ -1062,6 +1137,20 @@ class RayTracer:
         if libs()[1].chiaro_raytracer_layer_map(self._h, _ptr(m, C.c_uint32)):
             raise RuntimeError("layerMap: no adaptive render yet")
         return m
+
+    def denoise(self, levels=4, sigmaL=4.0, sigmaZ=0.1, sigmaA=0.1, normalSquarings=5) -> np.ndarray:
+        """The variance-guided a-trous filter over the frame of the last rayTraceUntil / rayTraceAdaptive (with its
+        layer map); exportImage / normalizeImage / getData act on the result until the next rayTrace*.  Raises for
+        any other frame -- its moments are not complete -- and with gpus > 1.  Returns the denoised frame."""
+        if libs()[1].chiaro_raytracer_denoise(self._h, int(levels), float(sigmaL), float(sigmaZ), float(sigmaA),
+                                              int(normalSquarings)):
+            raise RuntimeError("denoise: " + _host_err())
+        return self.denoisedData()
+
+    def denoisedData(self):
+        """The denoised frame [yres][xres][3], or None when denoise() has not run on this frame."""
+        p = libs()[1].chiaro_raytracer_denoised(self._h)
+        return np.ctypeslib.as_array(p, shape=(self.yres, self.xres, 3)).copy() if p else None
 
     def lastNoise(self) -> dict:
         st = CrNoiseStats()

@@ -5,6 +5,7 @@
 // per-launch HIP events.  No C++ exception or hipError_t crosses the ABI.
 #include "ctx.hpp"
 #include "adaptive.hpp"
+#include "denoise.hpp"
 #include "scenelayout.hpp"
 #include "wfplan.hpp"
 
@@ -753,6 +754,98 @@ int run_query_device(cr_ctx *c, uint32_t n, bool shadow, const float *orig, cons
 }
 } // namespace
 
+// ---- guide buffers and denoiser ----
+// b (d_guide or d_dn) at `need` bytes for work on st: a regrow first waits on the host for the last call that used
+// the scratch, another stream than that call's waits for it on the device
+static int dn_acquire(cr_ctx *c, DevBuf &b, size_t need, hipStream_t st) {
+    if (c->dn_pending && (!b.ptr || need > b.cap)) {
+        HIPCHK(hipEventSynchronize(c->dn_ev));
+        c->dn_pending = false;
+    } else if (c->dn_pending && st != c->dn_stream) {
+        HIPCHK(hipStreamWaitEvent(st, c->dn_ev, 0));
+    }
+    return grow(c, b, need, "guide / denoise scratch");
+}
+// after the call's work is enqueued (a failed call too: its earlier kernels may be on the stream)
+static int dn_release(cr_ctx *c, hipStream_t st, int rc) {
+    const hipError_t ev = hipEventRecord(c->dn_ev, st);
+    c->dn_pending = ev == hipSuccess;
+    c->dn_stream = st;
+    if (rc != CR_OK) return rc;
+    if (ev != hipSuccess) return hip_fail(c, ev, "hipEventRecord(denoise)");
+    return CR_OK;
+}
+// The guides of cam's xres x yres frame on st into whichever of albedo / normal / depth / rec is not null
+static int enqueue_guides(cr_ctx *c, const cr_camera *cam, uint32_t xres, uint32_t yres, float *albedo, float *normal,
+                          float *depth, float4 *rec, hipStream_t st) {
+    HIPCHK(hipSetDevice(c->device));
+    const uint64_t npix = (uint64_t)xres * yres;
+    const cr::GuideScratch gs = cr::guide_scratch(npix);
+    if (int r = dn_acquire(c, c->d_guide, gs.bytes, st)) return r;
+    char *base = c->d_guide.as<char>();
+    cr::GuideArgs G{};
+    G.S = c->S;
+    std::memcpy(G.cam, cam->eye, 3 * sizeof(float));
+    std::memcpy(G.cam + 3, cam->left_upper, 3 * sizeof(float));
+    std::memcpy(G.cam + 6, cam->dx, 3 * sizeof(float));
+    std::memcpy(G.cam + 9, cam->dy, 3 * sizeof(float));
+    G.xres = xres, G.yres = yres;
+    G.orig = (float *)(base + gs.orig), G.dir = (float *)(base + gs.dir);
+    uint32_t *hit = (uint32_t *)(base + gs.hit), *tri = (uint32_t *)(base + gs.tri);
+    float *bary = (float *)(base + gs.bary), *dist = (float *)(base + gs.dist);
+    G.hit = hit, G.tri = tri, G.bary = bary, G.dist = dist;
+    G.albedo = albedo, G.normal = normal, G.depth = depth, G.rec = rec;
+    int rc = CR_OK;
+    if (int e = cr::launch_guide_rays(G, st)) rc = hip_fail(c, (hipError_t)e, "guide ray kernel launch");
+    // the device query path, on the caller's stream: cr_intersect_device's routing, kernels and bits
+    if (!rc) rc = run_query_device(c, (uint32_t)npix, false, G.orig, G.dir, nullptr, nullptr, hit, tri, bary, dist, st);
+    if (!rc)
+        if (int e = cr::launch_guide_shade(G, st)) rc = hip_fail(c, (hipError_t)e, "guide shade kernel launch");
+    return dn_release(c, st, rc);
+}
+// The filter on st.  rec: the packed guide record already in the ctx's scratch (cr_denoise: guide_shade wrote it),
+// else albedo / normal / depth are packed first.  The scratch (d_dn) is acquired by the caller.
+static int enqueue_denoise(cr_ctx *c, uint32_t xres, uint32_t yres, uint32_t layers, uint32_t spp,
+                           const cr_denoise_params *dp, const float *frame, const float *m2, const uint32_t *map,
+                           const float *albedo, const float *normal, const float *depth, bool packed, float *out,
+                           float *var_out, hipStream_t st) {
+    const uint64_t npix = (uint64_t)xres * yres;
+    const cr::DnScratch sc = cr::dn_scratch(npix, dp->levels);
+    char *base = c->d_dn.as<char>();
+    cr::DnArgs D{};
+    D.xres = xres, D.yres = yres;
+    D.squarings = dp->normal_squarings;
+    D.spp = spp;
+    D.n = (float)(layers * spp);
+    D.sl2 = dp->sigma_l * dp->sigma_l;
+    D.inv_sa2 = 1.f / (dp->sigma_a * dp->sigma_a);
+    D.layer_map = map;
+    D.frame = frame, D.m2 = m2;
+    D.albedo = albedo, D.normal = normal, D.depth = depth;
+    D.rec = dp->levels ? (float4 *)(base + sc.guide) : nullptr;
+    D.out = out, D.var_out = var_out;
+    float4 *pp[2] = {dp->levels > 0 ? (float4 *)(base + sc.frame[0]) : nullptr,
+                     dp->levels > 1 ? (float4 *)(base + sc.frame[1]) : nullptr};
+    if (dp->levels && !packed)
+        if (int e = cr::launch_guide_pack(D, st)) return hip_fail(c, (hipError_t)e, "guide pack kernel launch");
+    D.dst = pp[0];
+    if (int e = cr::launch_var_init(D, st)) return hip_fail(c, (hipError_t)e, "variance kernel launch");
+    for (const cr::DnLevel &L : cr::dn_levels(dp->levels)) {
+        D.step = L.step;
+        D.sz_step = dp->sigma_z * (float)L.step;
+        D.src = pp[L.src];
+        D.dst = L.dst < 0 ? nullptr : pp[L.dst];
+        if (int e = cr::launch_atrous(D, L.lds, st)) return hip_fail(c, (hipError_t)e, "a-trous kernel launch");
+    }
+    return CR_OK;
+}
+static int check_denoise_args(cr_ctx *c, uint32_t xres, uint32_t yres, uint32_t layers, uint32_t spp,
+                              const cr_denoise_params *dp) {
+    if (const char *m = cr::dn_check_params(dp)) return fail(c, CR_E_INVALID, m);
+    if (const char *m = cr::dn_check_shape(xres, yres, layers, spp)) return fail(c, CR_E_INVALID, m);
+    return CR_OK;
+}
+
 extern "C" {
 
 cr_ctx *cr_create(int device) {
@@ -772,6 +865,7 @@ cr_ctx *cr_create(int device) {
         c->lane_ev[0].create(false) != hipSuccess || c->lane_ev[1].create(false) != hipSuccess ||
         c->hcnt.create(4) != hipSuccess || c->ev0.create(true) != hipSuccess || c->ev1.create(true) != hipSuccess ||
         c->q_ev.create(false) != hipSuccess || c->sel_ev.create(false) != hipSuccess ||
+        c->dn_ev.create(false) != hipSuccess ||
         c->d_counters.grow(cr::CTR_SLOTS * sizeof(unsigned long long)) != CR_OK) {
         delete c; // all or nothing: what was created goes now, while its device is current
         return (c = new cr_ctx())->err = "device init failed", c;
@@ -786,6 +880,7 @@ void cr_destroy(cr_ctx *c) {
         release_dist(c); // the communicator before its tile, gather and flag buffers
         if (c->q_pending) hipEventSynchronize(c->q_ev); // a pending query still uses d_query
         if (c->sel_pending) hipEventSynchronize(c->sel_ev); // ... a pending selection d_select
+        if (c->dn_pending) hipEventSynchronize(c->dn_ev);   // ... a pending guide or filter call d_guide / d_dn
     }
     delete c; // (a ctx without a device holds no handle: cr_create)
 }
@@ -1091,6 +1186,95 @@ int cr_render_adaptive(cr_ctx *c, const cr_camera *cam, const cr_render_params *
     if (layers_out) HIPCHK(hipMemcpyAsync(layers_out, map, (size_t)npix * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     *stats_out = out;
+    return CR_OK;
+}
+
+void cr_denoise_params_default(cr_denoise_params *out) {
+    if (out) cr::dn_defaults(*out);
+}
+void cr_denoise_struct_sizes(uint32_t *params_bytes) {
+    if (params_bytes) *params_bytes = (uint32_t)sizeof(cr_denoise_params);
+}
+
+int cr_guides_device(cr_ctx *c, const cr_camera *cam, uint32_t xres, uint32_t yres, float *d_albedo, float *d_normal,
+                     float *d_depth, void *stream) {
+    if (!c) return CR_E_INVALID;
+    if (!cam || (!d_albedo && !d_normal && !d_depth)) return fail(c, CR_E_INVALID, "null camera, or no guide output");
+    if (const char *m = cr::dn_check_shape(xres, yres, 1, 1)) return fail(c, CR_E_INVALID, m);
+    if (int rc = enter(c, false)) return rc;
+    if (!c->has_scene) return fail(c, CR_E_NOSCENE, "no scene uploaded");
+    return enqueue_guides(c, cam, xres, yres, d_albedo, d_normal, d_depth, nullptr, (hipStream_t)stream);
+}
+
+int cr_guides(cr_ctx *c, const cr_camera *cam, uint32_t xres, uint32_t yres, float *albedo, float *normal,
+              float *depth) {
+    if (!c) return CR_E_INVALID;
+    if (!cam || (!albedo && !normal && !depth)) return fail(c, CR_E_INVALID, "null camera, or no guide output");
+    if (const char *m = cr::dn_check_shape(xres, yres, 1, 1)) return fail(c, CR_E_INVALID, m);
+    if (int rc = enter(c)) return rc;
+    if (!c->has_scene) return fail(c, CR_E_NOSCENE, "no scene uploaded");
+    const size_t npix = (size_t)xres * yres;
+    DevBuf buf;
+    if (int r = grow(c, buf, npix * 7 * sizeof(float), "guide buffers")) return r;
+    float *da = buf.as<float>(), *dn = da + 3 * npix, *dz = dn + 3 * npix;
+    if (int rc = enqueue_guides(c, cam, xres, yres, albedo ? da : nullptr, normal ? dn : nullptr, depth ? dz : nullptr,
+                                nullptr, c->stream))
+        return rc;
+    if (albedo) HIPCHK(hipMemcpyAsync(albedo, da, 3 * npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (normal) HIPCHK(hipMemcpyAsync(normal, dn, 3 * npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (depth) HIPCHK(hipMemcpyAsync(depth, dz, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return CR_OK;
+}
+
+int cr_denoise_device(cr_ctx *c, uint32_t xres, uint32_t yres, uint32_t layers, uint32_t spp,
+                      const cr_denoise_params *dp, const float *d_frame, const float *d_m2, const uint32_t *d_layer_map,
+                      const float *d_albedo, const float *d_normal, const float *d_depth, float *d_out,
+                      float *d_var_out, void *stream) {
+    if (!c) return CR_E_INVALID;
+    if (!d_frame || !d_m2 || !d_albedo || !d_normal || !d_depth || !d_out)
+        return fail(c, CR_E_INVALID, "null frame / moment frame / guide / output");
+    if (int r = check_denoise_args(c, xres, yres, layers, spp, dp)) return r;
+    if (int rc = enter(c)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (int r = dn_acquire(c, c->d_dn, cr::dn_scratch((uint64_t)xres * yres, dp->levels).bytes, st)) return r;
+    const int rc = enqueue_denoise(c, xres, yres, layers, spp, dp, d_frame, d_m2, d_layer_map, d_albedo, d_normal,
+                                   d_depth, false, d_out, d_var_out, st);
+    return dn_release(c, st, rc);
+}
+
+int cr_denoise(cr_ctx *c, const cr_camera *cam, uint32_t xres, uint32_t yres, uint32_t layers, uint32_t spp,
+               const cr_denoise_params *dp, const uint32_t *layer_map, float *out, float *var_out) {
+    if (!c) return CR_E_INVALID;
+    if (!cam || !out) return fail(c, CR_E_INVALID, "null camera / output");
+    if (int r = check_denoise_args(c, xres, yres, layers, spp, dp)) return r;
+    if (int rc = enter(c)) return rc;
+    if (!c->has_scene) return fail(c, CR_E_NOSCENE, "no scene uploaded");
+    const size_t npix = (size_t)xres * yres;
+    if (c->d_accum.count<float>() != 3 * npix || c->d_accum2.count<float>() != 3 * npix || !c->d_accum.ptr ||
+        !c->d_accum2.ptr)
+        return fail(c, CR_E_INVALID, "cr_denoise: no frame and moment accumulator of this size (render with "
+                                     "cr_render_layers_noise / cr_render_until / cr_render_adaptive first)");
+    if (int r = grow(c, c->d_dn_out, npix * 4 * sizeof(float))) return r;
+    if (layer_map) {
+        if (int r = grow(c, c->d_dn_map, npix * sizeof(uint32_t))) return r;
+        HIPCHK(hipMemcpyAsync(c->d_dn_map.ptr, layer_map, npix * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    }
+    const cr::DnScratch sc = cr::dn_scratch(npix, dp->levels);
+    if (int r = dn_acquire(c, c->d_dn, sc.bytes, c->stream)) return r;
+    // the guides straight into the filter's packed record (no level: the filter reads no guide)
+    if (dp->levels)
+        if (int rc = enqueue_guides(c, cam, xres, yres, nullptr, nullptr, nullptr,
+                                    (float4 *)(c->d_dn.as<char>() + sc.guide), c->stream))
+            return rc;
+    float *d_out = c->d_dn_out.as<float>(), *d_var = d_out + 3 * npix;
+    const int rc = enqueue_denoise(c, xres, yres, layers, spp, dp, c->d_accum.as<float>(), c->d_accum2.as<float>(),
+                                   layer_map ? c->d_dn_map.as<uint32_t>() : nullptr, nullptr, nullptr, nullptr, true,
+                                   d_out, d_var, c->stream);
+    if (int r = dn_release(c, c->stream, rc)) return r;
+    HIPCHK(hipMemcpyAsync(out, d_out, 3 * npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (var_out) HIPCHK(hipMemcpyAsync(var_out, d_var, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
     return CR_OK;
 }
 

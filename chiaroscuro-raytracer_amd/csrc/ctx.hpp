@@ -60,6 +60,14 @@ struct cr_ctx : cr::CtxOptions { // (the options, cr_set_option's table: ctxopts
     crx::Event sel_ev;
     bool sel_pending = false;
     hipStream_t sel_stream = nullptr;
+    // guide buffers and denoiser (cr_guides* / cr_denoise*), grow-only: the guide rays and hits (denoise.hpp
+    // guide_scratch), the packed guide record and ping-pong frames (dn_scratch); cr_denoise's device copy of the
+    // caller's layer map and its outputs.  dn_ev is recorded after each call that used d_guide / d_dn: one on
+    // another stream than the last waits for it (cr_noise_select_device's rule), one that regrows them synchronises
+    crx::DevBuf d_guide, d_dn, d_dn_map, d_dn_out;
+    crx::Event dn_ev;
+    bool dn_pending = false;
+    hipStream_t dn_stream = nullptr;
     crx::DevBuf d_cull;      // camera-ray cull boxes, one per leaf reference (+ 4), per render
     crx::DevBuf d_cull_node; // ... their per-leaf unions, one per kd node
     cr_counters last{};

@@ -211,6 +211,43 @@ int launch_tile_list(uint32_t xres, uint32_t yres, uint32_t tile, uint32_t *out,
 // map[list[i]] = value for the n entries of list that are pixels (list null: map[i] = value for i < n)
 int launch_list_fill(uint32_t *map, const uint32_t *list, uint32_t n, uint32_t npix, uint32_t value, hipStream_t st);
 
+// denoise.hip: the guide buffers of the first hit and the a-trous filter (cr_guides_device / cr_denoise_device;
+// include/chiaro_hip.h "guide buffers and denoiser").
+// guide_rays writes one ray per pixel, through the pixel centre, into orig / dir [npix][3]; the batch then goes
+// through cr_intersect_device's path; guide_shade turns the hits into the outputs that are not null: albedo and
+// normal [npix][3], depth [npix], and the packed record rec [npix][2] = {albedo, depth}, {normal, 0}.
+struct GuideArgs {
+    DevScene S;
+    float cam[12]; // eye, leftUpper, dx, dy
+    uint32_t xres, yres;
+    float *orig, *dir;
+    const uint32_t *hit, *tri;
+    const float *bary, *dist;
+    float *albedo, *normal, *depth;
+    float4 *rec;
+};
+int launch_guide_rays(const GuideArgs &G, hipStream_t st);
+int launch_guide_shade(const GuideArgs &G, hipStream_t st);
+// The filter's three kernels: guide_pack (the caller's three guide arrays -> rec), var_init ((frame, m2) -> the
+// pixel's colour and the variance of its mean, as a float4 of ping-pong frame dst, or as out / var_out when no
+// level runs) and atrous (one level: src -> dst, or -> out / var_out for the last).
+struct DnArgs {
+    uint32_t xres, yres;
+    uint32_t step, squarings, spp;
+    float n;                   // (float)(layers * spp); with a layer map (float)(map * spp) per pixel
+    float sl2, sz_step, inv_sa2; // sigma_l * sigma_l, sigma_z * (float)step, 1 / (sigma_a * sigma_a)
+    const uint32_t *layer_map; // [npix] or null
+    const float *frame, *m2;   // [npix][3]
+    const float *albedo, *normal, *depth;
+    float4 *rec;               // [npix][2]
+    const float4 *src;         // [npix] {colour, variance}
+    float4 *dst;               // [npix], or null: out / var_out
+    float *out, *var_out;      // [npix][3], [npix] (var_out may be null)
+};
+int launch_guide_pack(const DnArgs &D, hipStream_t st);
+int launch_var_init(const DnArgs &D, hipStream_t st);
+int launch_atrous(const DnArgs &D, bool lds, hipStream_t st);
+
 // Wavefront path tracer (wavefront.hip, cr_set_option "kernel" 2): the paths of
 // work items [w0, w0 + P) advance one bounce per generation through separate
 // kernels (camera, closest trace, shade, shadow trace, bounce) that exchange

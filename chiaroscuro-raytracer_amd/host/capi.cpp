@@ -334,6 +334,17 @@ int chiaro_raytracer_layer_map(const chiaro_raytracer *r, uint32_t *layers_out) 
     std::memcpy(layers_out, r->r->layerMap().data(), r->r->layerMap().size() * sizeof(uint32_t));
     return CR_OK;
 }
+int chiaro_raytracer_denoise(chiaro_raytracer *r, uint32_t levels, float sigma_l, float sigma_z, float sigma_a,
+                             uint32_t normal_squarings) {
+    if (!r) return CR_E_INVALID;
+    return guard(
+        [&]() -> int {
+            r->r->denoise(levels, sigma_l, sigma_z, sigma_a, normal_squarings);
+            return CR_OK;
+        },
+        CR_E_HIP);
+}
+const float *chiaro_raytracer_denoised(const chiaro_raytracer *r) { return r ? r->r->denoisedData() : nullptr; }
 void chiaro_noise_struct_sizes(uint32_t *params_bytes, uint32_t *stats_bytes) {
     if (params_bytes) *params_bytes = (uint32_t)sizeof(cr_noise_params);
     if (stats_bytes) *stats_bytes = (uint32_t)sizeof(cr_noise_stats);

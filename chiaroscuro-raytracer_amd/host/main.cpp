@@ -14,6 +14,8 @@
 // (RayTracer::rayTraceUntil); N of "layers N" is then the most layers to render.
 // Extra token "adaptive T" (this build): further layers only for the pixels whose relative error exceeds T
 // (RayTracer::rayTraceAdaptive); N of "layers N" is then the most layers of any pixel.
+// Extra token "denoise N" (this build, with "noise T" or "adaptive T" only -- the renders that keep the frame's
+// moments): the frame is filtered with N a-trous levels (RayTracer::denoise) before it is exported.
 #include "model.hpp"
 #include "raytracer.hpp"
 #include "scene.hpp"
@@ -30,6 +32,7 @@ int main(int argc, char **argv) {
     unsigned layers = 1;
     float noise = -1.f;    // "noise T": T >= 0
     float adaptive = -1.f; // "adaptive T": T >= 0
+    int denoise = -1;      // "denoise N": 0 <= N <= 8 levels
     std::vector<char *> args;
     for (int i = 0; i < argc; i++) {
         if (i > 1 && !std::strcmp(argv[i], "layers") && i + 1 < argc) {
@@ -52,7 +55,21 @@ int main(int argc, char **argv) {
             }
             continue;
         }
+        if (i > 1 && !std::strcmp(argv[i], "denoise") && i + 1 < argc) {
+            char *end = nullptr;
+            const long n = std::strtol(argv[++i], &end, 10);
+            if (end == argv[i] || *end || n < 0 || n > 8) {
+                std::fprintf(stderr, "chiaroscuro: denoise takes a number of levels, 0..8\n");
+                return 1;
+            }
+            denoise = (int)n;
+            continue;
+        }
         args.push_back(argv[i]);
+    }
+    if (denoise >= 0 && noise < 0.f && adaptive < 0.f) {
+        std::fprintf(stderr, "chiaroscuro: denoise needs the frame's moments: use it with noise T or adaptive T\n");
+        return 1;
     }
     try {
         chiaro::Scene scene((int)args.size(), args.data());
@@ -84,6 +101,11 @@ int main(int argc, char **argv) {
             renderer.rayTraceLayers(layers, scene.VP, scene.LA, scene.UP, scene.yview);
         std::fprintf(stderr, "layers 1..%u: %.3f s, %llu rays\n", renderer.layers(), renderer.lastSeconds(),
                      (unsigned long long)(renderer.lastCounters().closest + renderer.lastCounters().shadow));
+        if (denoise >= 0) {
+            renderer.denoise((unsigned)denoise);
+            std::fprintf(stderr, "denoise %d: %d a-trous level(s) over %u layer(s) x %u spp%s\n", denoise, denoise,
+                         renderer.layers(), scene.samples, adaptive >= 0.f ? ", per-pixel layer map" : "");
+        }
         renderer.exportImage(scene.renderPath.c_str());
     } catch (const std::exception &e) {
         std::fprintf(stderr, "chiaroscuro: %s\n", e.what());

@@ -106,6 +106,7 @@ void RayTracer::rayTrace(vec3 eye, vec3 center, vec3 up, float yview) { rayTrace
 void RayTracer::rayTraceLayers(unsigned n, vec3 eye, vec3 center, vec3 up, float yview) {
     if (n < 1) return;
     noiseTracked_ = false; // (these layers keep no moments: a later rayTraceUntil starts over)
+    showDenoised_ = false;
     mixedLayers_ = false;
     // rayTracer.cpp:24 -- including the reference's `(lastUp == lastUp)`: a
     // change of `up` alone does not reset the accumulation.
@@ -177,6 +178,7 @@ unsigned RayTracer::rayTraceUntil(float threshold, unsigned maxLayers, vec3 eye,
                                   float floor, unsigned checkEvery, uint64_t maxAbove) {
     if (group_) throw std::runtime_error("chiaro: rayTraceUntil renders on one GPU (gpus 1)");
     if (maxLayers < 1) throw std::runtime_error("chiaro: rayTraceUntil: maxLayers must be >= 1");
+    showDenoised_ = false;
     // rayTraceLayers' rule (rayTracer.cpp:24), and the frame's moments must be complete to go on with it
     const bool newLayer = noiseTracked_ && (eye == lastEye) && (center == lastCenter) && (lastUp == lastUp) &&
                           (yview == lastYview);
@@ -206,6 +208,7 @@ unsigned RayTracer::rayTraceUntil(float threshold, unsigned maxLayers, vec3 eye,
     p.tile = 32;
     const cr_noise_params np{threshold, floor};
     cr_noise_stats st{};
+    momentCam_ = cam;
     if (cr_render_until(ctx_, &cam, &p, 1, maxLayers, checkEvery, &np, maxAbove, pixels.data(), &st) != CR_OK) {
         // (the accumulators may hold any number of this call's layers: the next render starts over)
         layers_ = 0;
@@ -246,6 +249,8 @@ uint64_t RayTracer::rayTraceAdaptive(float threshold, unsigned maxLayers, vec3 e
     // the frame is no progressive state, before or after: whatever follows starts at layer 1
     layers_ = 0;
     noiseTracked_ = false;
+    showDenoised_ = false;
+    momentCam_ = cam;
     lastEye = lastCenter = lastUp = vec3(FLT_MAX);
     lastYview = -1;
     layerMap_.assign((size_t)scene.xres * scene.yres, 0u);
@@ -262,6 +267,19 @@ uint64_t RayTracer::rayTraceAdaptive(float threshold, unsigned maxLayers, vec3 e
     for (float v : pixels) maxVal = maxVal > v ? maxVal : v;
     lastSeconds_ = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
     return st.pixel_layers;
+}
+
+void RayTracer::denoise(unsigned levels, float sigmaL, float sigmaZ, float sigmaA, unsigned normalSquarings) {
+    if (group_) throw std::runtime_error("chiaro: denoise filters on one GPU (gpus 1)");
+    if (!layers_ || !(noiseTracked_ || mixedLayers_))
+        throw std::runtime_error("chiaro: denoise: the frame's moments are not complete (render it with rayTraceUntil "
+                                 "or rayTraceAdaptive)");
+    const cr_denoise_params dp{levels, sigmaL, sigmaZ, sigmaA, normalSquarings};
+    denoised_.resize(pixels.size());
+    if (cr_denoise(ctx_, &momentCam_, scene.xres, scene.yres, layers_, scene.samples, &dp,
+                   mixedLayers_ ? layerMap_.data() : nullptr, denoised_.data(), nullptr) != CR_OK)
+        throw std::runtime_error(std::string("chiaro: denoise failed: ") + cr_last_error(ctx_));
+    showDenoised_ = true;
 }
 
 std::vector<float> RayTracer::noiseMap() {
@@ -317,6 +335,7 @@ void RayTracer::resume(const char *path) {
     layers_ = h.layers;
     mixedLayers_ = false;
     noiseTracked_ = false; // (the checkpoint holds the frame only)
+    showDenoised_ = false;
     lastEye = vec3(h.eye[0], h.eye[1], h.eye[2]);
     lastCenter = vec3(h.center[0], h.center[1], h.center[2]);
     lastUp = vec3(h.up[0], h.up[1], h.up[2]);
@@ -333,6 +352,16 @@ void RayTracer::normalizeImage(float exposure, float defog, float kneeLow, float
     if (exposure == FLT_MAX) exposure = scene.exposure;
     cr_tonemap_params t;
     cr_tonemap_setup(exposure, defog, kneeLow, kneeHigh, gamma, &t);
+    if (showDenoised_) {
+        // cr_tonemap reads the device accumulator: it holds the denoised frame for this one call and the rendered
+        // frame -- `pixels`, the host copy of exactly those bits -- again afterwards (gpus 1: denoise() saw to that)
+        int rc = cr_set_accumulator(ctx_, scene.xres, scene.yres, denoised_.data());
+        if (rc == CR_OK) rc = cr_tonemap(ctx_, &t, scene.xres, scene.yres, data.data());
+        const int back = cr_set_accumulator(ctx_, scene.xres, scene.yres, pixels.data());
+        if (rc != CR_OK || back != CR_OK)
+            throw std::runtime_error(std::string("chiaro: tonemap failed: ") + cr_last_error(ctx_));
+        return;
+    }
     if (group_) {
         if (cr_group_tonemap(group_, &t, scene.xres, scene.yres, data.data()) != CR_OK)
             throw std::runtime_error(std::string("chiaro: tonemap failed: ") + cr_group_last_error(group_));
@@ -376,13 +405,13 @@ void RayTracer::exportImage(const char *filename) {
     }
     if (ends_with(fn, ".pfm")) {
         o << "PF\n" << W << " " << H << "\n-1.0\n";
-        for (unsigned y = H; y-- > 0;) o.write((const char *)&pixels[3 * (size_t)y * W], (std::streamsize)(12 * W));
+        for (unsigned y = H; y-- > 0;) o.write((const char *)&shown()[3 * (size_t)y * W], (std::streamsize)(12 * W));
     } else if (ends_with(fn, ".hdr")) { // Radiance RGBE, flat scanlines
         o << "#?RADIANCE\nFORMAT=32-bit_rle_rgbe\n\n-Y " << H << " +X " << W << "\n";
         std::vector<unsigned char> row(4 * (size_t)W);
         for (unsigned y = 0; y < H; y++) {
             for (unsigned x = 0; x < W; x++) {
-                const float *p = &pixels[3 * ((size_t)y * W + x)];
+                const float *p = &shown()[3 * ((size_t)y * W + x)];
                 float v = std::max(p[0], std::max(p[1], p[2]));
                 unsigned char *e = &row[4 * (size_t)x];
                 if (v < 1e-32f) {
@@ -397,7 +426,7 @@ void RayTracer::exportImage(const char *filename) {
             o.write((const char *)row.data(), (std::streamsize)row.size());
         }
     } else if (ends_with(fn, ".exr")) { // HALF B, G, R, PIZ: what FreeImage_Save(FIF_EXR, ..., 0) writes
-        const std::vector<unsigned char> f = chiaro::exr_encode(pixels.data(), (int)W, (int)H);
+        const std::vector<unsigned char> f = chiaro::exr_encode(shown().data(), (int)W, (int)H);
         o.write((const char *)f.data(), (std::streamsize)f.size());
     } else { // 8-bit: rows of `data` are bottom-up (rayTracer.cpp:217), write top-down
         normalizeImage();

@@ -57,6 +57,15 @@ class RayTracer {
                               float yview = 1.f, float floor = 1e-3f, unsigned minLayers = 1, unsigned checkEvery = 1);
     const std::vector<uint32_t> &layerMap() const { return layerMap_; } // [yres][xres]; empty before rayTraceAdaptive
     const cr_adaptive_stats &lastAdaptive() const { return adaptive_; }
+    /* This build: the variance-guided a-trous filter (cr_denoise, include/chiaro_hip.h "guide buffers and denoiser")
+     * over the frame of the last rayTraceUntil or rayTraceAdaptive -- the renders that keep the frame's moments; an
+     * adaptive frame is filtered with its layer map.  Fills the denoised buffer (denoisedData()); exportImage,
+     * normalizeImage and getData act on it until the next rayTrace* call.  The rendered frame (pixelData()) and the
+     * progressive state are untouched: rayTraceUntil continues bit-identically afterwards.  Throws
+     * std::runtime_error when the frame's moments are not complete (any other render), and with gpus > 1. */
+    void denoise(unsigned levels = 4, float sigmaL = 4.f, float sigmaZ = .1f, float sigmaA = .1f,
+                 unsigned normalSquarings = 5);
+    const float *denoisedData() const { return showDenoised_ ? denoised_.data() : nullptr; } // [yres][xres][3]
     /* The statistic of the last rayTraceUntil's last check, and the error map [yres][xres] of its frame. */
     const cr_noise_stats &lastNoise() const { return noise_; }
     std::vector<float> noiseMap();
@@ -97,6 +106,10 @@ class RayTracer {
     cr_adaptive_stats adaptive_{};
     std::vector<uint32_t> layerMap_;
     bool mixedLayers_ = false; // the frame is rayTraceAdaptive's: its pixels hold different layer counts
+    cr_camera momentCam_{};    // the camera of the last rayTraceUntil / rayTraceAdaptive (denoise's guides)
+    std::vector<float> denoised_;
+    bool showDenoised_ = false; // denoise() ran on this frame: export / normalize / getData act on denoised_
+    const std::vector<float> &shown() const { return showDenoised_ ? denoised_ : pixels; }
     double lastSeconds_ = 0.0;
     // rayTracer.cpp:18-22 progressive-layer state (per instance here, not function-static)
     unsigned layers_ = 0;

@@ -43,6 +43,9 @@
  *                        the same accumulation with further layers rendered only for the pixels that are still
  *                        noisy: a render of listed pixels, the selection of the pixels above a threshold, and the
  *                        loop of the two (no reference counterpart: its sample loop covers every pixel, :55-58).
+ *   cr_guides_device / cr_guides / cr_denoise_device / cr_denoise
+ *                        the albedo, normal and depth of each pixel's first hit, and a variance-guided a-trous filter
+ *                        over the frame that uses them (no reference counterpart: its frame is the samples' mean, :59-64).
  *   cr_intersect         KDTree::intersectRay       (src/kdtree.cpp:210-216)
  *   cr_intersect_shadow  KDTree::intersectShadowRay (src/kdtree.cpp:283-290)
  *   cr_intersect_device / cr_intersect_shadow_device
@@ -415,6 +418,86 @@ int cr_noise_select_device(cr_ctx *ctx, uint32_t xres, uint32_t yres, uint32_t l
 int cr_render_adaptive(cr_ctx *ctx, const cr_camera *cam, const cr_render_params *p, const cr_adaptive_params *ap,
                        const cr_noise_params *np, float *frame_out, float *m2_out, uint32_t *layers_out,
                        cr_adaptive_stats *stats_out);
+
+/* ------------------------------------------------ guide buffers and denoiser --
+ * A clean picture at a low sample count: the feature buffers of each pixel's first hit, and an edge-avoiding a-trous
+ * filter steered by them and by the variance the noise block already estimates.  The reference has no counterpart
+ * (its frame is what its samples average to, src/rayTracer.cpp:59-64); like the noise estimate this is a definition
+ * of this build, and every bit of it is pinned by the oracle's pieces plus float32 arithmetic.
+ *
+ * GUIDES (cr_guides_device / cr_guides).  One ray per pixel (x, y) through its centre: origin cam->eye, direction
+ *   (left_upper + dx * sx) + dy * sy,  sx = (float)x + 0.5f, sy = (float)y + 0.5f
+ * -- the camera ray's affine form without the jitter, not normalised.  The batch is traced as cr_intersect_device
+ * traces it (the same routing and kernels, on the caller's stream), so hit, triangle, barycentrics (bx, by) and
+ * distance are cr_intersect's bit for bit.  Per pixel:
+ *   albedo [yres][xres][3]  the triangle's Kd; for a textured triangle the texel at the render's own uv,
+ *                           bz = 1 - bx - by, u = (ua.x * bz + ub.x * bx) + uc.x * by, v likewise; a miss: (0, 0, 0)
+ *   normal [yres][xres][3]  the triangle's material normal n, normalised as the render normalises
+ *                           (n * (1 / sqrt((n.x * n.x + n.y * n.y) + n.z * n.z))); a miss: (0, 0, 0); a zero material
+ *                           normal gives what that expression gives (NaN), which the filter below copes with
+ *   depth  [yres][xres]     the hit distance in units of the direction; a miss: -1.0f
+ * Any of the three outputs may be null, not all three.  cr_guides_device is stream-ordered and does not synchronise
+ * the host; cr_get_counters is not touched.  Errors: arguments (CR_E_INVALID), then the device (CR_E_HIP), then the
+ * scene (CR_E_NOSCENE).
+ *
+ * FILTER (cr_denoise_device / cr_denoise).  float32, round to nearest, no contraction, IEEE division; operations in
+ * the order written; taps in row-major order, j = 0..4 outer, i = 0..4 inner.  Inputs: the frame C, the moment frame
+ * m2, n = (float)(layers * spp) -- with a layer map (uint32 [yres][xres], an adaptive frame's per-pixel layer counts)
+ * n = (float)(map * spp) per pixel -- and the guides A (albedo), N (normal), Z (depth).
+ *   initial variance of the pixel's mean: per channel v = m2 - C * C; v = v > 0 ? v : 0 (a NaN too); v = v / n;
+ *     var = (v_r + v_g) + v_b
+ *   level `it` (step s = 1 << it), for each pixel p:
+ *     vb = the 3x3 blur of var around p (neighbours at distance 1, coordinates clamped to the frame), weights
+ *          G[j] * G[i], G = {1/4, 1/2, 1/4}, accumulated from 0 in row-major order (vb = vb + (G[j] * G[i]) * var_q)
+ *     den = (sigma_l * sigma_l) * vb + 1e-8f;  b = (C_r + C_g) + C_b
+ *     tap (j, i) at q = p + s * (i - 2, j - 2), w0 = H[j] * H[i], H = {1/16, 1/4, 3/8, 1/4, 1/16}; a tap outside the
+ *     frame is skipped; the centre tap has w = w0; any other tap:
+ *       1. dl = b_q - b_p;  t = 1 / (1 + (dl * dl) / den);  w = w0 * (t * t)
+ *       2. da = A_q - A_p;  d2 = ((da_r * da_r + da_g * da_g) + da_b * da_b) * (1 / (sigma_a * sigma_a));
+ *          t = 1 / (1 + d2);  w = w * (t * t)
+ *       3. both pixels hits (Z >= 0): dn = (N_p.x * N_q.x + N_p.y * N_q.y) + N_p.z * N_q.z;  dn = dn > 0 ? dn : 0;
+ *          dn = dn * dn, normal_squarings times;  dz = (Z_q - Z_p) / ((sigma_z * (float)s) * (Z_p > Z_q ? Z_p : Z_q));
+ *          t = 1 / (1 + dz * dz);  w = w * (dn * (t * t))
+ *       4. exactly one of the two a hit: the tap is skipped
+ *       5. w not > 0 (zero, negative, NaN): the tap is skipped -- it adds nothing to any sum
+ *     sums from 0: sw = sw + w;  sc = sc + w * C_q (per channel);  sv = sv + (w * w) * var_q
+ *     C' = sc / sw;  var' = sv / (sw * sw)
+ * The centre tap always counts, so sw >= 9/64; a NaN pixel stays NaN and, by 5, does not spread; levels == 0
+ * returns the frame and the initial variance bit for bit.
+ * cr_denoise_device is stream-ordered, does not synchronise the host and needs no scene; d_layer_map and d_var_out
+ * [yres][xres] may be null; outputs must not alias inputs.  The ping-pong frames and the packed guide record live in
+ * a grow-only scratch of the ctx: a call on another stream than the last one that used it first waits (on the
+ * device) for that one, as cr_noise_select_device does, and a call that has to regrow it -- a larger frame than any
+ * before -- waits for that one on the host, as cr_intersect_device does (cr_guides_device's rays and hits live in
+ * such a scratch too, under the same rule).  cr_denoise runs on the ctx's two accumulators (the frame
+ * of the last cr_render_layers_noise / cr_render_until / cr_render_adaptive), computes the guides itself, and leaves
+ * both accumulators as they are: a progressive render continues bit-identically afterwards.  layer_map (host,
+ * cr_render_adaptive's) and var_out may be null.
+ * Errors: CR_E_INVALID (checked before the device) for a null pointer, levels > 8, normal_squarings > 8, a sigma not
+ * finite or <= 0, xres or yres 0, layers * spp == 0 or above 32 bits; cr_denoise also for accumulators of another
+ * size (after the device and scene checks).
+ * Not covered: albedo demodulation (directly visible emitters break it), temporal reprojection, MODE_TILES,
+ * cr_group_*, cr_comm_* and the distributed renders; the checkpoint format is unchanged. */
+typedef struct cr_denoise_params {
+    uint32_t levels;            /* a-trous iterations, 0..8; level i uses step 1 << i */
+    float sigma_l;              /* brightness, in standard deviations (> 0) */
+    float sigma_z;              /* relative depth change per pixel of step (> 0) */
+    float sigma_a;              /* albedo distance (> 0) */
+    uint32_t normal_squarings;  /* the normal weight is max(0, n . n')^(2^k), k = 0..8 */
+} cr_denoise_params;
+void cr_denoise_params_default(cr_denoise_params *out); /* 4, 4.0, 0.1, 0.1, 5 */
+/* sizeof the structure as this library was built */
+void cr_denoise_struct_sizes(uint32_t *params_bytes);
+int cr_guides_device(cr_ctx *ctx, const cr_camera *cam, uint32_t xres, uint32_t yres, float *d_albedo, float *d_normal,
+                     float *d_depth, void *stream);
+int cr_guides(cr_ctx *ctx, const cr_camera *cam, uint32_t xres, uint32_t yres, float *albedo, float *normal,
+              float *depth);
+int cr_denoise_device(cr_ctx *ctx, uint32_t xres, uint32_t yres, uint32_t layers, uint32_t spp,
+                      const cr_denoise_params *dp, const float *d_frame, const float *d_m2, const uint32_t *d_layer_map,
+                      const float *d_albedo, const float *d_normal, const float *d_depth, float *d_out,
+                      float *d_var_out, void *stream);
+int cr_denoise(cr_ctx *ctx, const cr_camera *cam, uint32_t xres, uint32_t yres, uint32_t layers, uint32_t spp,
+               const cr_denoise_params *dp, const uint32_t *layer_map, float *out, float *var_out);
 
 /* Ray queries (host arrays). dir need not be normalised (the reference does not). */
 int cr_intersect(cr_ctx *ctx, uint32_t n, const float *orig, const float *dir, uint32_t *hit, uint32_t *tri,

@@ -11,6 +11,8 @@
  *   chiaro_raytracer_raytrace_adaptive / _adaptive / _layer_map
  *                            the same accumulation with further layers only where the frame is still noisy (this
  *                            build; cr_render_adaptive)
+ *   chiaro_raytracer_denoise / _denoised
+ *                            an edge-avoiding filter over such a frame (this build; cr_denoise)
  *   chiaro_raytracer_raytrace_until / _noise / _noise_map
  *                            rayTrace repeated until a noise target is met (this build; the accumulation of
  *                            src/rayTracer.cpp:18-33,59-64 with a second-moment frame, cr_render_until)
@@ -114,6 +116,15 @@ int chiaro_raytracer_raytrace_adaptive(chiaro_raytracer *r, float threshold, uin
                                        uint32_t min_layers, uint32_t check_every, uint64_t *pixel_layers_out);
 int chiaro_raytracer_adaptive(const chiaro_raytracer *r, cr_adaptive_stats *out);
 int chiaro_raytracer_layer_map(const chiaro_raytracer *r, uint32_t *layers_out);
+/* RayTracer::denoise: the variance-guided a-trous filter (cr_denoise, include/chiaro_hip.h "guide buffers and
+ * denoiser") over the frame of the last chiaro_raytracer_raytrace_until / _raytrace_adaptive (whose layer map it
+ * then uses).  chiaro_raytracer_data / _normalize / _export act on the denoised frame until the next raytrace call;
+ * chiaro_raytracer_pixels stays the rendered frame, and the progressive state is untouched.  CR_E_HIP with
+ * chiaro_last_error when the frame's moments are not complete (any other render) or with gpus > 1.
+ * chiaro_raytracer_denoised: the denoised frame [yres][xres][3], NULL when there is none. */
+int chiaro_raytracer_denoise(chiaro_raytracer *r, uint32_t levels, float sigma_l, float sigma_z, float sigma_a,
+                             uint32_t normal_squarings);
+const float *chiaro_raytracer_denoised(const chiaro_raytracer *r);
 const float *chiaro_raytracer_pixels(const chiaro_raytracer *r);
 const uint8_t *chiaro_raytracer_data(chiaro_raytracer *r);
 float chiaro_raytracer_maxval(const chiaro_raytracer *r);
