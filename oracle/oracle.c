@@ -744,6 +744,17 @@ void or_rng_draws(uint32_t seed, uint32_t layer, uint32_t pixel, uint32_t sample
     rng_t r = rng_make(seed, layer, pixel, sample);
     for (uint32_t i = 0; i < n; i++) out[i] = rng_u32(&r);
 }
+/* RNG KAT: the two distributions the integrator draws through, on a raw (key, ctr) stream */
+void or_rng_uniform_kat(uint32_t key, uint32_t ctr, float a, float b, float *out, uint32_t *ctr_out) {
+    rng_t r; r.key = key; r.ctr = ctr;
+    *out = rng_uniform(&r, a, b);
+    *ctr_out = r.ctr;
+}
+void or_rng_index_kat(uint32_t key, uint32_t ctr, uint32_t n, uint32_t *out, uint32_t *ctr_out) {
+    rng_t r; r.key = key; r.ctr = ctr;
+    *out = rng_index(&r, n);
+    *ctr_out = r.ctr;
+}
 
 /* src/rayTracer.cpp:52-70 */
 void or_render(or_scene *s, const float cam[12], uint32_t xres, uint32_t yres, uint32_t spp, int k,

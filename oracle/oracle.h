@@ -80,6 +80,10 @@ void or_tex_lookup(const or_scene *s, int tex, float u, float v, float out[3]);
 
 /* RNG stream (DESIGN.md "RNG"): n raw u32 draws of stream (seed, layer, pixel, sample). */
 void or_rng_draws(uint32_t seed, uint32_t layer, uint32_t pixel, uint32_t sample, uint32_t n, uint32_t *out);
+/* RNG KAT: rng_uniform(a, b) / rng_index(n) of the render loop on the raw stream (key, ctr); ctr_out = the
+ * counter after the call (draws consumed = ctr_out - ctr). */
+void or_rng_uniform_kat(uint32_t key, uint32_t ctr, float a, float b, float *out, uint32_t *ctr_out);
+void or_rng_index_kat(uint32_t key, uint32_t ctr, uint32_t n, uint32_t *out, uint32_t *ctr_out);
 
 /* Path KAT (G4): radiance of one camera sample, recursion exactly as sendRay. */
 void or_path(or_scene *s, const float cam[12], uint32_t xres, uint32_t yres, int k, const float bg[3],

@@ -61,6 +61,8 @@ def lib():
             "or_sincos": (None, [C.c_float, FP, FP]),
             "or_tex_lookup": (None, [P, C.c_int, C.c_float, C.c_float, FP]),
             "or_rng_draws": (None, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, UP]),
+            "or_rng_uniform_kat": (None, [C.c_uint32, C.c_uint32, C.c_float, C.c_float, FP, UP]),
+            "or_rng_index_kat": (None, [C.c_uint32, C.c_uint32, C.c_uint32, UP, UP]),
             "or_path": (None, [P, FP, C.c_uint32, C.c_uint32, C.c_int, FP, C.c_uint32, C.c_uint32, C.c_uint32,
                                C.c_uint32, C.c_uint32, FP]),
             "or_render": (None, [P, FP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, FP, C.c_uint32, C.c_uint32,
@@ -229,6 +231,20 @@ def rng_draws(seed, layer, pixel, sample, n):
     out = np.zeros(n, np.uint32)
     lib().or_rng_draws(seed, layer, pixel, sample, n, _p(out, C.c_uint32))
     return out
+
+
+def rng_uniform_kat(key, ctr, a, b):
+    """rng_uniform(a, b) on the raw stream (key, ctr): (value as float32, counter after the call)."""
+    out, c = np.zeros(1, np.float32), np.zeros(1, np.uint32)
+    lib().or_rng_uniform_kat(int(key), int(ctr), float(a), float(b), _p(out), _p(c, C.c_uint32))
+    return out[0], int(c[0])
+
+
+def rng_index_kat(key, ctr, n):
+    """rng_index(n) on the raw stream (key, ctr): (index, counter after the call)."""
+    out, c = np.zeros(1, np.uint32), np.zeros(1, np.uint32)
+    lib().or_rng_index_kat(int(key), int(ctr), int(n), _p(out, C.c_uint32), _p(c, C.c_uint32))
+    return int(out[0]), int(c[0])
 
 
 def tonemap(rgb, exposure, defog=0.0, knee_low=0.0, knee_high=5.0, gamma=2.2):
