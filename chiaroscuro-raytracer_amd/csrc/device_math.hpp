@@ -71,6 +71,32 @@ __device__ __forceinline__ float div_by_rcp_wave(float a, float b, float y) {
     if (__ballot(!in)) q = in ? q : a / b;
     return q;
 }
+// The side of a kd split plane the ray starts on (kdtree.cpp:267-268, 334-335):
+//     below = (oa < split) || (oa == split && da <= 0)
+// from a = split - oa, which the step has formed for the division.  For finite oa and split the difference
+// has the sign of the exact one and is zero only for equality (f32 denormals are kept, so a nonzero
+// difference never rounds to zero; an overflow keeps its sign), so
+//     da <= 0 (-0 and +0 included):  below = a >= 0 = -a < 2^-149 (the smallest float above zero)
+//     da > 0, or da NaN:             below = a > 0  = -a < 0
+// and a NaN a (a NaN coordinate) compares false as both of the reference's comparisons do.  One compare
+// of da, one select, one compare of a, and no mask arithmetic (scripts/kdstep_check.c walks the cases).
+// (-a against +2^-149 and not a against -2^-149: the bits of 2^-149 are the integer 1, an inline constant
+// of the select, and the negation is an operand modifier of the compare; -2^-149 is a 32-bit literal that
+// the compiler keeps in a VGPR of its own through the whole kernel.)
+__device__ __forceinline__ bool kd_below(float a, float da) { return -a < (da <= 0.f ? 0x1p-149f : 0.f); }
+
+// div_by_rcp_wave for dividends with |a| <= 2^20: y is a number only for 2^-40 <= |b| <= 2^40
+// (rcp_for_div, trav_begin), so |y| <= 2^40 and |q0| <= 2^60 (a power of two: rounding cannot pass it) --
+// the upper range test cannot fire and is left out.  A NaN y (an axis outside rcp_for_div's range) makes q0
+// NaN, which fails the remaining test and takes the full division as before.  Checked against a / b over
+// 1.7e10 pairs of that domain, half of them next to rounding midpoints (scripts/kdstep_check.c).
+__device__ __forceinline__ float div_by_rcp_wave_bounded(float a, float b, float y) {
+    const float q0 = a * y;
+    float q = __builtin_fmaf(__builtin_fmaf(-q0, b, a), y, q0);
+    const bool in = fabsf(q0) >= 0x1p-60f;
+    if (__ballot(!in)) q = in ? q : a / b;
+    return q;
+}
 // RN(1/a): hardware reciprocal (1 ulp) + one Newton step with fma.  Checked
 // exhaustively over every float with 2^-100 <= |a| <= 2^100 on gfx950
 // (tests/test_gpu_numerics.py).

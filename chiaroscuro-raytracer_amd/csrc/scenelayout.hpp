@@ -242,7 +242,10 @@ inline int scene_layout(const cr_scene_desc *d, uint32_t node_bfs, SceneLayout &
     out.S.n_nodes = d->n_nodes;
     out.S.bmin = make_float3(d->box_min[0], d->box_min[1], d->box_min[2]);
     out.S.bmax = make_float3(d->box_max[0], d->box_max[1], d->box_max[2]);
-    out.S.db = (float)lc_db; // every origin (a hit point + 0.001 n) and vertex lies in the padded box
+    // every origin (a hit point + 0.001 n) and vertex lies in the padded box.  db <= 2^19: a split distance's
+    // dividend split - o_a is at most 2 db <= 2^20, the domain of the fixed trace kernels' one-sided short
+    // division (wfbuilds.hpp wf_short_division_scene, which the launchers check per render)
+    out.S.db = (float)lc_db;
     out.tree_depth = tree_depth;
     out.stack_depth = std::max(tree_depth, std::max(d->max_depth, 1u));
     out.n_refs = d->n_refs;

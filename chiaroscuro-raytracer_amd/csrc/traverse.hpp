@@ -271,7 +271,9 @@ __device__ __forceinline__ void trav_pop(uint2 *ring, uint2 *gstk, uint32_t gstr
 
 // One kd decision at inner node nd (kdtree.cpp:258-275): T.node = the child to descend into (child + k,
 // k returned), the far child pushed when both are crossed, the ring's oldest entry spilled when it is full.
-// Reads C::FD (the split division) and C::BF (the decision as selects, a branch only around the push).
+// Reads C::FD (the split division; with C::FIX its one-sided form) and C::BF (the decision as selects, a
+// branch only around the push).  The instruction stream of one decision, and why `below`, the child's index
+// and the pushed child are written as they are: DESIGN.md §3.26.
 // (o, d by reference and bdim = blockDim.x, tid = threadIdx.x read once by trav_round, as its lambdas hold
 // them: by value, or read here, kernels came out changed -- DESIGN.md §3.24.)
 template <class C>
@@ -282,39 +284,49 @@ __device__ __forceinline__ uint32_t kd_step(uint2 nd, uint2 *ring, uint32_t bdim
     const uint32_t a = nd.y & 3u;
     const float split = __uint_as_float(nd.x);
     const float oa = comp(o, a), da = comp(d, a);
-    const float tsplit = C::FD ? div_by_rcp_wave(split - oa, da, comp(T.r, a)) : split_distance(split, oa, da);
-    const uint32_t below = (oa < split) || (oa == split && da <= 0);
+    // (FIX: the launchers take such a kernel only for a scene inside wf_short_division_scene's bound)
+    const float tsplit = !C::FD    ? split_distance(split, oa, da)
+                         : C::FIX ? div_by_rcp_wave_bounded(split - oa, da, comp(T.r, a))
+                                  : div_by_rcp_wave(split - oa, da, comp(T.r, a));
+    const bool below = kd_below(split - oa, da);
     const uint32_t child = nd.y >> 2;
     uint32_t k;
+    // the branching form keeps `below` as 0 / 1 in a register (the empty asm pins it there): as a lane mask it
+    // would be merged over the three branches by exec arithmetic on the scalar unit, ~7 instructions a step
+    uint32_t bw = below;
+    if (!C::BF) asm("" : "+v"(bw));
     if (C::BF) { // (bitwise logic on the lane masks: no short-circuit exec branches)
         const bool near_only = (tsplit >= T.tmax) | (tsplit < 0);
         const bool far_only = !near_only & (tsplit <= T.tmin);
         const bool push = !near_only & !far_only;
-        k = far_only ? below : 1u - below;
+        // far_only ? below : 1 - below, on the lane masks; the child's index here, in the block of the
+        // compares, where the lane mask is the add's carry-in (past the push it is a select and an add)
+        k = below ^ (near_only | !(tsplit <= T.tmin));
+        T.node = child + k;
         if (push) {
             const uint32_t slot = (T.sp & (R - 1)) * bdim + tid;
             if (T.nl == R) P.load(false, 8);
             if (T.nl == R) gstack_at(gstk, T.sp - R, gstride, gid) = ring[slot]; // spill the oldest
-            ring[slot] = make_uint2(child + below, __float_as_uint(T.tmax));
+            ring[slot] = make_uint2(2u * child + 1u - T.node, __float_as_uint(T.tmax)); // the other child
+            T.sp++;
         }
         T.nl = push && T.nl < R ? T.nl + 1 : T.nl;
-        T.sp += push ? 1u : 0u;
         T.tmax = push ? tsplit : T.tmax;
     } else if (tsplit >= T.tmax || tsplit < 0) {
-        k = 1u - below;
+        k = 1u - bw;
     } else if (tsplit <= T.tmin) {
-        k = below;
+        k = bw;
     } else {
-        const uint2 e = make_uint2(child + below, __float_as_uint(T.tmax));
+        const uint2 e = make_uint2(child + bw, __float_as_uint(T.tmax));
         const uint32_t slot = (T.sp & (R - 1)) * bdim + tid;
         if (T.nl == R) gstack_at(gstk, T.sp - R, gstride, gid) = ring[slot]; // spill the oldest
         else T.nl++;
         ring[slot] = e;
         T.sp++;
         T.tmax = tsplit;
-        k = 1u - below;
+        k = 1u - bw;
     }
-    T.node = child + k;
+    if (!C::BF) T.node = child + k;
     return k;
 }
 

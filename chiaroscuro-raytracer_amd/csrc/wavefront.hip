@@ -1494,7 +1494,7 @@ static int launch_wf(WfKernel k, uint32_t blocks, size_t lds, hipStream_t s, con
     return 0;
 }
 static bool fixed_options(const RenderArgs &A, const WfArgs &W) {
-    return wf_fixed_options(W.vis_mark, W.ended_only, A.lc_debug);
+    return wf_fixed_options(W.vis_mark, W.ended_only, A.lc_debug) && wf_short_division_scene(A.S.db);
 }
 // One thread per leaf reference: its cull box for this render's camera (camcull.hpp),
 // from the record's A, e1, e2 -- the floats the triangle test uses.  Boxes

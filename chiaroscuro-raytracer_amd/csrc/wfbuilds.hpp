@@ -45,7 +45,9 @@ struct TraceDefaults {
     static constexpr bool LXD = false;    // LX builds: the exchange's prefix by a DPP scan
     // the options every real run leaves at their defaults fixed at compile time: WfArgs::vis_mark 1,
     // WfArgs::ended_only 0 (no overlapped tail), RenderArgs::lc_debug 0 -- the launchers take such an
-    // instantiation only for a launch whose options have these values (tc::Fixed, wf_fixed_options)
+    // instantiation only for a launch whose options have these values (tc::Fixed, wf_fixed_options).  It also
+    // fixes a fact of the scene: |coordinate| <= 2^19 (wf_short_division_scene), under which the FD builds'
+    // split division drops its upper range test (device_math.hpp div_by_rcp_wave_bounded)
     static constexpr bool FIX = false;
 };
 
@@ -394,6 +396,13 @@ constexpr size_t wf_ring_bytes(int ring) { return (size_t)ring * WF_TRACE_BLOCK 
 constexpr bool wf_fixed_options(int vis_mark, uint32_t ended_only, int lc_debug) {
     return vis_mark == 1 && ended_only == 0u && lc_debug == 0;
 }
+// True when the split division of a render's secondary and shadow rays stays below its upper range bound by
+// the scene alone: the dividend is split - o_a with |split| <= db and |o_a| <= db (DevScene::db: every vertex,
+// so every split plane, and every origin the render makes lie in the padded box), the reciprocal is at most
+// 2^40 (rcp_for_div), so |q0| <= 2 db 2^40 <= 2^60 once db <= 2^19.  A scene outside it renders with the
+// build's generic kernels, whose division tests both bounds.  (A caller's ray queries never take a fixed
+// kernel: wf_query_kernel.)
+constexpr bool wf_short_division_scene(float db) { return db <= 0x1p19f; }
 // A selected camera trace: `id` indexes PacketKernels when `packet`, else TraceKernels.
 struct CameraSel {
     int packet, id;
