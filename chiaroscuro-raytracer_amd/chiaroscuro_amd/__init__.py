@@ -218,6 +218,21 @@ def denoise_params(levels=None, sigma_l=None, sigma_z=None, sigma_a=None, normal
     return dp
 
 
+class CrTemporalParams(C.Structure):
+    """cr_temporal_params (include/chiaro_hip.h "temporal reprojection")."""
+    _fields_ = [("depth_tol", C.c_float), ("normal_min", C.c_float), ("max_history", C.c_uint32)]
+
+
+def temporal_params(depth_tol=None, normal_min=None, max_history=None) -> CrTemporalParams:
+    """cr_temporal_params_default (0.05, 0.9, 65536) with the given fields replaced."""
+    tp = CrTemporalParams()
+    libs()[0].cr_temporal_params_default(C.byref(tp))
+    for k, v in (("depth_tol", depth_tol), ("normal_min", normal_min), ("max_history", max_history)):
+        if v is not None:
+            setattr(tp, k, v)
+    return tp
+
+
 def tonemap_params(exposure, defog=0.0, knee_low=0.0, knee_high=5.0, gamma=2.2) -> CrTonemapParams:
     """cr_tonemap_setup: normalizeImage's host scalars (src/rayTracer.cpp:196-205)."""
     t = CrTonemapParams()
@@ -246,7 +261,9 @@ HIP_SYMBOLS = ("cr_create", "cr_destroy", "cr_last_error", "cr_upload_scene", "c
                "cr_adaptive_struct_sizes", "cr_render_layers_list_device", "cr_noise_select_device",
                "cr_render_adaptive",
                "cr_denoise_params_default", "cr_denoise_struct_sizes", "cr_guides_device", "cr_guides",
-               "cr_denoise_device", "cr_denoise")
+               "cr_denoise_device", "cr_denoise",
+               "cr_temporal_params_default", "cr_temporal_struct_sizes", "cr_reproject_device", "cr_render_temporal",
+               "cr_temporal_reset", "cr_temporal_history")
 HOST_SYMBOLS = ("chiaro_last_error", "chiaro_scene_create", "chiaro_scene_info_get", "chiaro_scene_destroy",
                 "chiaro_model_create", "chiaro_model_load", "chiaro_model_num_meshes", "chiaro_model_num_triangles",
                 "chiaro_model_num_textures", "chiaro_model_triangles", "chiaro_model_texture",
@@ -265,7 +282,8 @@ HOST_SYMBOLS = ("chiaro_last_error", "chiaro_scene_create", "chiaro_scene_info_g
                 "chiaro_preview_camera_replay", "chiaro_raytracer_raytrace_until", "chiaro_raytracer_noise",
                 "chiaro_raytracer_noise_map", "chiaro_noise_struct_sizes", "chiaro_raytracer_raytrace_adaptive",
                 "chiaro_raytracer_adaptive", "chiaro_raytracer_layer_map", "chiaro_raytracer_denoise",
-                "chiaro_raytracer_denoised")
+                "chiaro_raytracer_denoised", "chiaro_raytracer_raytrace_temporal", "chiaro_raytracer_reset_temporal",
+                "chiaro_raytracer_count_map", "chiaro_preview_set_temporal")
 
 P = C.c_void_p
 FP = C.POINTER(C.c_float)
@@ -392,6 +410,15 @@ def libs():
          [CTX, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, DP, P, P, P, P, P, P, P, P, P])
     _sig(hip, "cr_denoise", C.c_int,
          [CTX, C.POINTER(CrCamera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, DP, UP, FP, FP])
+    TP = C.POINTER(CrTemporalParams)
+    _sig(hip, "cr_temporal_params_default", None, [TP])
+    _sig(hip, "cr_temporal_struct_sizes", None, [UP])
+    _sig(hip, "cr_reproject_device", C.c_int,
+         [CTX, C.POINTER(CrCamera), C.POINTER(CrCamera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, TP] + [P] * 14)
+    _sig(hip, "cr_render_temporal", C.c_int,
+         [CTX, C.POINTER(CrCamera), C.POINTER(CrRenderParams), C.c_uint32, TP, DP, FP, UP])
+    _sig(hip, "cr_temporal_reset", C.c_int, [CTX])
+    _sig(hip, "cr_temporal_history", C.c_int, [CTX, FP, FP, UP])
 
     _sig(host, "chiaro_last_error", C.c_char_p, [])
     _sig(host, "chiaro_scene_create", P, [C.c_int, C.POINTER(C.c_char_p)])
@@ -427,6 +454,10 @@ def libs():
     _sig(host, "chiaro_raytracer_layer_map", C.c_int, [P, UP])
     _sig(host, "chiaro_raytracer_denoise", C.c_int, [P, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_uint32])
     _sig(host, "chiaro_raytracer_denoised", FP, [P])
+    _sig(host, "chiaro_raytracer_raytrace_temporal", C.c_int, [P, FP, FP, FP, C.c_float, C.c_uint32, C.c_uint32, UP])
+    _sig(host, "chiaro_raytracer_reset_temporal", C.c_int, [P])
+    _sig(host, "chiaro_raytracer_count_map", C.c_int, [P, UP])
+    _sig(host, "chiaro_preview_set_temporal", C.c_int, [P, C.c_int])
     _sig(host, "chiaro_raytracer_pixels", FP, [P])
     _sig(host, "chiaro_raytracer_data", C.POINTER(C.c_uint8), [P])
     _sig(host, "chiaro_raytracer_maxval", C.c_float, [P])
@@ -781,6 +812,48 @@ class Device:
                                        None if lm is None else _ptr(lm, C.c_uint32), _ptr(out),
                                        _ptr(var) if want_var else None), "cr_denoise")
         return out, var
+
+    def reproject_device(self, cam_cur: CrCamera, cam_prev: CrCamera, xres: int, yres: int, layers: int, spp: int,
+                         tp: CrTemporalParams, d_frame_ptr: int, d_m2_ptr: int, d_layer_map_ptr: int, d_normal_ptr: int,
+                         d_depth_ptr: int, d_hist_frame_ptr: int, d_hist_m2_ptr: int, d_hist_count_ptr: int,
+                         d_hist_normal_ptr: int, d_hist_depth_ptr: int, d_out_ptr: int, d_m2_out_ptr: int,
+                         d_count_out_ptr: int, stream: int = 0):
+        """cr_reproject_device: the history (frame, m2 [yres][xres][3], count uint32 [yres][xres], normal, depth) of
+        cam_prev carried to cam_cur through the current guides and merged with the current frame and moment frame
+        into d_out, d_m2_out, d_count_out; d_layer_map_ptr may be 0.  Enqueued on `stream`."""
+        v = lambda p: C.c_void_p(p or None)
+        self._chk(libs()[0].cr_reproject_device(self._c, C.byref(cam_cur), C.byref(cam_prev), int(xres), int(yres),
+                                                int(layers), int(spp), C.byref(tp), v(d_frame_ptr), v(d_m2_ptr),
+                                                v(d_layer_map_ptr), v(d_normal_ptr), v(d_depth_ptr),
+                                                v(d_hist_frame_ptr), v(d_hist_m2_ptr), v(d_hist_count_ptr),
+                                                v(d_hist_normal_ptr), v(d_hist_depth_ptr), v(d_out_ptr),
+                                                v(d_m2_out_ptr), v(d_count_out_ptr), C.c_void_p(stream)),
+                  "cr_reproject_device")
+
+    def render_temporal(self, cam: CrCamera, p: CrRenderParams, nlayers: int = 1, tp: CrTemporalParams | None = None,
+                        dp: CrDenoiseParams | None = None):
+        """cr_render_temporal: layers 1 .. nlayers at cam merged with the ctx's reprojected history (which the result
+        replaces); dp: the returned frame is the a-trous filter of the merge.  Successive frames need different
+        p.seed.  Returns (frame [yres][xres][3], count uint32 [yres][xres])."""
+        tp = tp if tp is not None else temporal_params()
+        out = np.zeros((p.yres, p.xres, 3), np.float32)
+        count = np.zeros((p.yres, p.xres), np.uint32)
+        self._chk(libs()[0].cr_render_temporal(self._c, C.byref(cam), C.byref(p), int(nlayers), C.byref(tp),
+                                               C.byref(dp) if dp is not None else None, _ptr(out),
+                                               _ptr(count, C.c_uint32)), "cr_render_temporal")
+        return out, count
+
+    def temporal_reset(self):
+        """cr_temporal_reset: the next cr_render_temporal starts a new history."""
+        self._chk(libs()[0].cr_temporal_reset(self._c), "cr_temporal_reset")
+
+    def temporal_history(self, xres: int, yres: int):
+        """cr_temporal_history: (frame, m2 [yres][xres][3], count uint32 [yres][xres]) of the stored history, whose
+        size the caller names."""
+        f, m = np.zeros((yres, xres, 3), np.float32), np.zeros((yres, xres, 3), np.float32)
+        k = np.zeros((yres, xres), np.uint32)
+        self._chk(libs()[0].cr_temporal_history(self._c, _ptr(f), _ptr(m), _ptr(k, C.c_uint32)), "cr_temporal_history")
+        return f, m, k
 
     def render_device(self, cam, p, d_frame_ptr: int, stream: int = 0):
         self._chk(libs()[0].cr_render_device(self._c, C.byref(cam), C.byref(p), C.c_void_p(d_frame_ptr),
@@ -1152,6 +1225,28 @@ class RayTracer:
         p = libs()[1].chiaro_raytracer_denoised(self._h)
         return np.ctypeslib.as_array(p, shape=(self.yres, self.xres, 3)).copy() if p else None
 
+    def rayTraceTemporal(self, eye, center, up=(0.0, 1.0, 0.0), yview=1.0, layers=1, denoiseLevels=0) -> int:
+        """`layers` layers at this view merged with the history of the earlier rayTraceTemporal calls, reprojected to
+        it (cr_render_temporal; the seed advances by one per call); denoiseLevels > 0: the shown frame is filtered.
+        exportImage / normalizeImage / getData / denoisedData act on the result until the next rayTrace*.  Returns
+        the smallest non-zero sample count of the frame; countMap() is each pixel's."""
+        least = C.c_uint32(0)
+        rc = libs()[1].chiaro_raytracer_raytrace_temporal(self._h, _fa(eye), _fa(center), _fa(up), float(yview),
+                                                          int(layers), int(denoiseLevels), C.byref(least))
+        if rc:
+            raise RuntimeError("rayTraceTemporal: " + _host_err())
+        return int(least.value)
+
+    def resetTemporal(self):
+        if libs()[1].chiaro_raytracer_reset_temporal(self._h):
+            raise RuntimeError("resetTemporal: " + _host_err())
+
+    def countMap(self) -> np.ndarray:
+        m = np.zeros((self.yres, self.xres), np.uint32)
+        if libs()[1].chiaro_raytracer_count_map(self._h, _ptr(m, C.c_uint32)):
+            raise RuntimeError("countMap: no temporal render yet")
+        return m
+
     def lastNoise(self) -> dict:
         st = CrNoiseStats()
         libs()[1].chiaro_raytracer_noise(self._h, C.byref(st))
@@ -1238,6 +1333,11 @@ class Preview:
     def key(self, k: str, dt: float = 0.0, shift: bool = False):
         if libs()[1].chiaro_preview_key(self._p, self.KEYS[k], float(dt), int(shift)):
             raise RuntimeError("Preview.key: " + _host_err())
+
+    def set_temporal(self, on: bool):
+        """chiaro_preview_set_temporal: R renders through rayTraceTemporal (a moved camera keeps its history)."""
+        if libs()[1].chiaro_preview_set_temporal(self._p, int(bool(on))):
+            raise RuntimeError("Preview.set_temporal: " + _host_err())
 
     def mouse(self, dx: float, dy: float):
         libs()[1].chiaro_preview_mouse(self._p, float(dx), float(dy))

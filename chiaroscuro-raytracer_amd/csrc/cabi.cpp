@@ -7,6 +7,7 @@
 #include "adaptive.hpp"
 #include "denoise.hpp"
 #include "scenelayout.hpp"
+#include "temporal.hpp"
 #include "wfplan.hpp"
 
 #include <algorithm>
@@ -367,27 +368,28 @@ uint32_t crx::group_layers(cr_ctx *c, const cr_render_params *p, uint32_t want, 
 // moment accumulator takes the same layers.  *nl_out: the layers rendered; the passes' counters and times are
 // added to `sum`.
 static int render_layer_group(cr_ctx *c, const cr_camera *cam, const cr_render_params &g, uint32_t want, float *m2,
-                              crx::PassTotals &sum, uint32_t *nl_out) {
+                              crx::PassTotals &sum, uint32_t *nl_out, float *frame = nullptr) {
     uint32_t m = 1;
     const uint32_t nl = crx::group_layers(c, &g, std::min(LAYER_GROUP, want), &m);
     for (uint32_t k = 0; k < m; k++) {
         cr_render_params t = g;
         t.rank = k;
         t.nranks = m;
-        if (int rc = crx::run_render(c, cam, &t, c->d_accum.as<float>(), cr::MODE_BLEND, c->stream, nl, 0, 1, 0, m2))
+        if (int rc = crx::run_render(c, cam, &t, frame ? frame : c->d_accum.as<float>(), cr::MODE_BLEND, c->stream, nl,
+                                     0, 1, 0, m2))
             return rc;
         sum.add(c);
     }
     *nl_out = nl;
     return CR_OK;
 }
-// Layers q.layer .. + nlayers - 1 in pass groups
+// Layers q.layer .. + nlayers - 1 in pass groups (frame: another frame than the ctx's accumulator, m2 beside it)
 static int render_layer_groups(cr_ctx *c, const cr_camera *cam, const cr_render_params &q, uint32_t nlayers, float *m2,
-                               crx::PassTotals &sum) {
+                               crx::PassTotals &sum, float *frame = nullptr) {
     for (uint32_t done = 0, nl = 0; done < nlayers; done += nl) {
         cr_render_params g = q;
         g.layer = q.layer + done;
-        if (int rc = render_layer_group(c, cam, g, nlayers - done, m2, sum, &nl)) return rc;
+        if (int rc = render_layer_group(c, cam, g, nlayers - done, m2, sum, &nl, frame)) return rc;
     }
     return CR_OK;
 }
@@ -846,6 +848,93 @@ static int check_denoise_args(cr_ctx *c, uint32_t xres, uint32_t yres, uint32_t 
     return CR_OK;
 }
 
+// ---- temporal reprojection ----
+// The kernel's arguments but its arrays: the two cameras, the projector of the previous one, the parameters.
+// false: the previous camera's projector is degenerate.
+static bool reproject_args(cr::TpArgs &T, const cr_camera *cur, const cr_camera *prev, uint32_t xres, uint32_t yres,
+                           uint32_t layers, uint32_t spp, const cr_temporal_params *tp) {
+    cr::TpProjector pr;
+    if (!cr::tp_projector(*prev, pr)) return false;
+    T.xres = xres, T.yres = yres;
+    T.spp = spp, T.n_u = layers * spp;
+    T.max_history = tp->max_history;
+    T.depth_tol = tp->depth_tol, T.normal_min = tp->normal_min;
+    std::memcpy(T.cam, cur->eye, 3 * sizeof(float));
+    std::memcpy(T.cam + 3, cur->left_upper, 3 * sizeof(float));
+    std::memcpy(T.cam + 6, cur->dx, 3 * sizeof(float));
+    std::memcpy(T.cam + 9, cur->dy, 3 * sizeof(float));
+    std::memcpy(T.eye_p, prev->eye, 3 * sizeof(float));
+    std::memcpy(T.ra, pr.ra, sizeof(pr.ra));
+    std::memcpy(T.rb, pr.rb, sizeof(pr.rb));
+    std::memcpy(T.rc, pr.rc, sizeof(pr.rc));
+    T.det = pr.det;
+    return true;
+}
+// One side of the ctx's history (temporal.hpp tp_scratch)
+struct TpSide {
+    float *frame, *m2, *normal, *depth;
+    uint32_t *count;
+    float4 *rec;
+};
+static TpSide tp_side_of(cr_ctx *c, const cr::TpScratch &sc, uint32_t side) {
+    char *b = c->d_tp.as<char>() + (size_t)side * sc.side;
+    return TpSide{(float *)(b + sc.frame), (float *)(b + sc.m2), (float *)(b + sc.normal), (float *)(b + sc.depth),
+                  (uint32_t *)(b + sc.count), cr::TP_CTX_PACKED ? (float4 *)(b + sc.rec) : nullptr};
+}
+// cr_render_temporal behind its guards: everything enqueued on the ctx's stream; the caller copies out and waits
+static int render_temporal(cr_ctx *c, const cr_camera *cam, const cr_render_params &q, uint32_t nlayers,
+                           const cr_temporal_params *tp, const cr_denoise_params *dp, const cr::TpScratch &sc,
+                           float **shown) {
+    hipStream_t st = c->stream;
+    const uint32_t xres = q.xres, yres = q.yres;
+    const size_t npix = (size_t)xres * yres;
+    char *base = c->d_tp.as<char>();
+    float *cur = (float *)(base + sc.cur_frame), *cur2 = (float *)(base + sc.cur_m2);
+    float *albedo = dp ? (float *)(base + sc.cur_albedo) : nullptr;
+    const bool merge = c->tp_has;
+    const TpSide H = tp_side_of(c, sc, c->tp_side), N = tp_side_of(c, sc, c->tp_side ^ 1u);
+    c->tp_has = false; // (until the new history is whole)
+    HIPCHK(hipMemsetAsync(cur, 0, npix * 12, st));
+    HIPCHK(hipMemsetAsync(cur2, 0, npix * 12, st));
+    PassTotals sum;
+    if (int rc = render_layer_groups(c, cam, q, nlayers, cur2, sum, cur)) return rc;
+    sum.store(c);
+    if (int rc = enqueue_guides(c, cam, xres, yres, albedo, N.normal, N.depth, nullptr, st)) return rc;
+    if (merge) {
+        cr::TpArgs T{};
+        if (!reproject_args(T, cam, &c->tp_cam, xres, yres, nlayers, q.spp, tp))
+            return fail(c, CR_E_INVALID, "cr_render_temporal: the history's camera has no projector (det 0 or not finite)");
+        T.frame = cur, T.m2 = cur2, T.normal = N.normal, T.depth = N.depth;
+        T.hist_frame = H.frame, T.hist_m2 = H.m2, T.hist_count = H.count, T.hist_normal = H.normal;
+        T.hist_depth = H.depth, T.hist_rec = H.rec;
+        T.out = N.frame, T.m2_out = N.m2, T.count_out = N.count, T.rec_out = N.rec;
+        if (int e = cr::launch_reproject(T, cr::TP_CTX_PACKED != 0, st))
+            return hip_fail(c, (hipError_t)e, "reproject kernel launch");
+    } else {
+        HIPCHK(hipMemcpyAsync(N.frame, cur, npix * 12, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpyAsync(N.m2, cur2, npix * 12, hipMemcpyDeviceToDevice, st));
+        if (int e = cr::launch_list_fill(N.count, nullptr, (uint32_t)npix, (uint32_t)npix, nlayers * q.spp, st))
+            return hip_fail(c, (hipError_t)e, "history count fill launch");
+        if (N.rec)
+            if (int e = cr::launch_temporal_pack((uint32_t)npix, N.frame, N.m2, N.count, N.normal, N.depth, N.rec, st))
+                return hip_fail(c, (hipError_t)e, "history pack kernel launch");
+    }
+    c->tp_side ^= 1u;
+    c->tp_cam = *cam;
+    c->tp_x = xres, c->tp_y = yres;
+    c->tp_has = true;
+    *shown = N.frame;
+    if (dp) {
+        if (int r = grow(c, c->d_dn_out, npix * 4 * sizeof(float))) return r;
+        if (int r = dn_acquire(c, c->d_dn, cr::dn_scratch(npix, dp->levels).bytes, st)) return r;
+        const int rc = enqueue_denoise(c, xres, yres, 1, 1, dp, N.frame, N.m2, N.count, albedo, N.normal, N.depth, false,
+                                       c->d_dn_out.as<float>(), nullptr, st);
+        if (int r = dn_release(c, st, rc)) return r;
+        *shown = c->d_dn_out.as<float>();
+    }
+    return CR_OK;
+}
+
 extern "C" {
 
 cr_ctx *cr_create(int device) {
@@ -1274,6 +1363,90 @@ int cr_denoise(cr_ctx *c, const cr_camera *cam, uint32_t xres, uint32_t yres, ui
     if (int r = dn_release(c, c->stream, rc)) return r;
     HIPCHK(hipMemcpyAsync(out, d_out, 3 * npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     if (var_out) HIPCHK(hipMemcpyAsync(var_out, d_var, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return CR_OK;
+}
+
+void cr_temporal_params_default(cr_temporal_params *out) {
+    if (out) cr::tp_defaults(*out);
+}
+void cr_temporal_struct_sizes(uint32_t *params_bytes) {
+    if (params_bytes) *params_bytes = (uint32_t)sizeof(cr_temporal_params);
+}
+
+int cr_reproject_device(cr_ctx *c, const cr_camera *cam_cur, const cr_camera *cam_prev, uint32_t xres, uint32_t yres,
+                        uint32_t layers, uint32_t spp, const cr_temporal_params *tp, const float *d_frame,
+                        const float *d_m2, const uint32_t *d_layer_map, const float *d_normal, const float *d_depth,
+                        const float *d_hist_frame, const float *d_hist_m2, const uint32_t *d_hist_count,
+                        const float *d_hist_normal, const float *d_hist_depth, float *d_out, float *d_m2_out,
+                        uint32_t *d_count_out, void *stream) {
+    if (!c) return CR_E_INVALID;
+    if (!cam_cur || !cam_prev || !d_frame || !d_m2 || !d_normal || !d_depth || !d_hist_frame || !d_hist_m2 ||
+        !d_hist_count || !d_hist_normal || !d_hist_depth || !d_out || !d_m2_out || !d_count_out)
+        return fail(c, CR_E_INVALID, "null camera / frame / guide / history / output");
+    if (const char *m = cr::tp_check_params(tp)) return fail(c, CR_E_INVALID, m);
+    if (const char *m = cr::tp_check_shape(xres, yres)) return fail(c, CR_E_INVALID, m);
+    cr::TpArgs T{};
+    if (!reproject_args(T, cam_cur, cam_prev, xres, yres, layers, spp, tp))
+        return fail(c, CR_E_INVALID, "the previous camera has no projector (det 0 or not finite)");
+    if (int rc = enter(c)) return rc;
+    T.layer_map = d_layer_map;
+    T.frame = d_frame, T.m2 = d_m2, T.normal = d_normal, T.depth = d_depth;
+    T.hist_frame = d_hist_frame, T.hist_m2 = d_hist_m2, T.hist_count = d_hist_count;
+    T.hist_normal = d_hist_normal, T.hist_depth = d_hist_depth;
+    T.out = d_out, T.m2_out = d_m2_out, T.count_out = d_count_out;
+    if (int e = cr::launch_reproject(T, false, (hipStream_t)stream))
+        return hip_fail(c, (hipError_t)e, "reproject kernel launch");
+    return CR_OK;
+}
+
+int cr_render_temporal(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, uint32_t nlayers,
+                       const cr_temporal_params *tp, const cr_denoise_params *dp, float *out, uint32_t *count_out) {
+    if (!c) return CR_E_INVALID;
+    if (!cam || !p || !out || nlayers < 1) return fail(c, CR_E_INVALID, "null camera/params/output or no layers");
+    if (const char *m = cr::tp_check_params(tp)) return fail(c, CR_E_INVALID, m);
+    if (dp)
+        if (const char *m = cr::dn_check_params(dp)) return fail(c, CR_E_INVALID, m);
+    cr_render_params q = *p;
+    if (q.nranks == 0) q.nranks = 1;
+    if (q.layer != 1 || q.nranks != 1)
+        return fail(c, CR_E_INVALID, "cr_render_temporal: layer 1 of the whole frame (nranks 1)");
+    if (const char *m = cr::dn_check_shape(q.xres, q.yres, nlayers, q.spp)) return fail(c, CR_E_INVALID, m);
+    if (int rc = enter(c)) return rc;
+    if (!c->has_scene) return fail(c, CR_E_NOSCENE, "no scene uploaded");
+    if (int rc = check_params(c, &q)) return rc;
+    const size_t npix = (size_t)q.xres * q.yres;
+    const cr::TpScratch sc = cr::tp_scratch(npix, cr::TP_CTX_PACKED != 0);
+    if (c->tp_has && (c->tp_x != q.xres || c->tp_y != q.yres)) c->tp_has = false; // a history of another size
+    if (!c->d_tp.ptr || sc.bytes > c->d_tp.cap) c->tp_has = false;
+    if (int r = grow(c, c->d_tp, sc.bytes, "temporal history")) return r;
+    float *shown = nullptr;
+    if (int rc = render_temporal(c, cam, q, nlayers, tp, dp, sc, &shown)) {
+        hipStreamSynchronize(c->stream); // (what was enqueued uses the buffers)
+        return rc;
+    }
+    HIPCHK(hipMemcpyAsync(out, shown, npix * 12, hipMemcpyDeviceToHost, c->stream));
+    if (count_out)
+        HIPCHK(hipMemcpyAsync(count_out, tp_side_of(c, sc, c->tp_side).count, npix * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return CR_OK;
+}
+
+int cr_temporal_reset(cr_ctx *c) {
+    if (!c) return CR_E_INVALID;
+    if (int rc = enter(c, false)) return rc;
+    c->tp_has = false;
+    return CR_OK;
+}
+
+int cr_temporal_history(cr_ctx *c, float *frame, float *m2, uint32_t *count) {
+    if (int rc = enter(c)) return rc;
+    if (!c->tp_has) return fail(c, CR_E_INVALID, "cr_temporal_history: no history (cr_render_temporal first)");
+    const size_t npix = (size_t)c->tp_x * c->tp_y;
+    const TpSide H = tp_side_of(c, cr::tp_scratch(npix, cr::TP_CTX_PACKED != 0), c->tp_side);
+    if (frame) HIPCHK(hipMemcpyAsync(frame, H.frame, npix * 12, hipMemcpyDeviceToHost, c->stream));
+    if (m2) HIPCHK(hipMemcpyAsync(m2, H.m2, npix * 12, hipMemcpyDeviceToHost, c->stream));
+    if (count) HIPCHK(hipMemcpyAsync(count, H.count, npix * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return CR_OK;
 }

@@ -68,6 +68,13 @@ struct cr_ctx : cr::CtxOptions { // (the options, cr_set_option's table: ctxopts
     crx::Event dn_ev;
     bool dn_pending = false;
     hipStream_t dn_stream = nullptr;
+    // temporal reprojection (cr_render_temporal), grow-only: the double-buffered history and the current frame's own
+    // buffers (temporal.hpp tp_scratch).  tp_side is the side that holds the history of camera tp_cam at
+    // tp_x x tp_y, when tp_has; the calls run on the ctx's stream and return after it
+    crx::DevBuf d_tp;
+    bool tp_has = false;
+    uint32_t tp_side = 0, tp_x = 0, tp_y = 0;
+    cr_camera tp_cam{};
     crx::DevBuf d_cull;      // camera-ray cull boxes, one per leaf reference (+ 4), per render
     crx::DevBuf d_cull_node; // ... their per-leaf unions, one per kd node
     cr_counters last{};

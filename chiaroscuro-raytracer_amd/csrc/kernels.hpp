@@ -248,6 +248,36 @@ int launch_guide_pack(const DnArgs &D, hipStream_t st);
 int launch_var_init(const DnArgs &D, hipStream_t st);
 int launch_atrous(const DnArgs &D, bool lds, hipStream_t st);
 
+// temporal.hip: temporal reprojection (cr_reproject_device / cr_render_temporal; include/chiaro_hip.h "temporal
+// reprojection").  One gather kernel, a thread per pixel of the current frame: the pixel's first
+// hit projected into the previous camera, four bilinear taps of the history there, the merge with the current
+// samples.  The history is read as the five planar arrays, or (launch_reproject's `packed`) as hist_rec
+// [npix][3] = {H, K bits}, {H2, Zp}, {Np, 0}; rec_out, when not null, takes the result in that form beside the
+// planar outputs (normal and depth are the current frame's); temporal_pack builds such a record from planar arrays.
+struct TpArgs {
+    uint32_t xres, yres;
+    uint32_t spp, n_u;         // n_u = layers * spp (wrapping); with a layer map map * spp per pixel
+    uint32_t max_history;
+    float depth_tol, normal_min;
+    float cam[12];             // the current camera: eye, leftUpper, dx, dy
+    float eye_p[3];            // the previous camera's eye and its projector (temporal.hpp tp_projector)
+    float ra[3], rb[3], rc[3], det;
+    const uint32_t *layer_map; // [npix] or null
+    const float *frame, *m2;   // [npix][3] the current frame and moment frame
+    const float *normal, *depth; // [npix][3], [npix] the current guides
+    const float *hist_frame, *hist_m2; // [npix][3]
+    const uint32_t *hist_count;        // [npix]
+    const float *hist_normal, *hist_depth;
+    const float4 *hist_rec;    // [npix][3] (packed)
+    float *out, *m2_out;       // [npix][3]
+    uint32_t *count_out;       // [npix]
+    float4 *rec_out;           // [npix][3] or null
+};
+int launch_reproject(const TpArgs &T, bool packed, hipStream_t st);
+// rec[npix][3] from frame / m2 [npix][3], count [npix], normal [npix][3], depth [npix]
+int launch_temporal_pack(uint32_t npix, const float *frame, const float *m2, const uint32_t *count, const float *normal,
+                         const float *depth, float4 *rec, hipStream_t st);
+
 // Wavefront path tracer (wavefront.hip, cr_set_option "kernel" 2): the paths of
 // work items [w0, w0 + P) advance one bounce per generation through separate
 // kernels (camera, closest trace, shade, shadow trace, bounce) that exchange

@@ -345,6 +345,34 @@ int chiaro_raytracer_denoise(chiaro_raytracer *r, uint32_t levels, float sigma_l
         CR_E_HIP);
 }
 const float *chiaro_raytracer_denoised(const chiaro_raytracer *r) { return r ? r->r->denoisedData() : nullptr; }
+int chiaro_raytracer_raytrace_temporal(chiaro_raytracer *r, const float eye[3], const float center[3],
+                                       const float up[3], float yview, uint32_t layers, uint32_t denoise_levels,
+                                       uint32_t *min_count_out) {
+    if (!r || !eye || !center || !up || layers < 1) return CR_E_INVALID;
+    return guard(
+        [&]() -> int {
+            const uint32_t least =
+                r->r->rayTraceTemporal(vec3(eye[0], eye[1], eye[2]), vec3(center[0], center[1], center[2]),
+                                       vec3(up[0], up[1], up[2]), yview, layers, denoise_levels);
+            if (min_count_out) *min_count_out = least;
+            return CR_OK;
+        },
+        CR_E_HIP);
+}
+int chiaro_raytracer_reset_temporal(chiaro_raytracer *r) {
+    if (!r) return CR_E_INVALID;
+    return guard(
+        [&]() -> int {
+            r->r->resetTemporal();
+            return CR_OK;
+        },
+        CR_E_HIP);
+}
+int chiaro_raytracer_count_map(const chiaro_raytracer *r, uint32_t *counts_out) {
+    if (!r || !counts_out || r->r->countMap().empty()) return CR_E_INVALID;
+    std::memcpy(counts_out, r->r->countMap().data(), r->r->countMap().size() * sizeof(uint32_t));
+    return CR_OK;
+}
 void chiaro_noise_struct_sizes(uint32_t *params_bytes, uint32_t *stats_bytes) {
     if (params_bytes) *params_bytes = (uint32_t)sizeof(cr_noise_params);
     if (stats_bytes) *stats_bytes = (uint32_t)sizeof(cr_noise_stats);
@@ -522,6 +550,16 @@ int chiaro_preview_key(chiaro_preview *p, int key, float dt, int shift) {
             case CHIARO_KEY_SHIFT: P.shiftState(shift != 0); break;
             default: return CR_E_INVALID;
             }
+            return CR_OK;
+        },
+        CR_E_HIP);
+}
+
+int chiaro_preview_set_temporal(chiaro_preview *p, int on) {
+    if (!p) return CR_E_INVALID;
+    return guard(
+        [&]() -> int {
+            p->p->setTemporal(on != 0);
             return CR_OK;
         },
         CR_E_HIP);

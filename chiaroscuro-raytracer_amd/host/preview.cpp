@@ -75,8 +75,9 @@ PreviewSession::PreviewSession(Scene &s, RayTracer &r) : camera(s.VP, s.LA, s.UP
 // src/openglPreview.cpp:139-146, 247-251
 void PreviewSession::pressRender() {
     showRender = true;
-    renderer.rayTrace(camera.Position, camera.Front + camera.Position, camera.Up,
-                      (float)(2 * ::tan(camera.Zoom * M_PI / 360.)));
+    const float yview = (float)(2 * ::tan(camera.Zoom * M_PI / 360.));
+    if (temporal_) renderer.rayTraceTemporal(camera.Position, camera.Front + camera.Position, camera.Up, yview);
+    else renderer.rayTrace(camera.Position, camera.Front + camera.Position, camera.Up, yview);
     renders++;
     updateScreen();
 }

@@ -34,6 +34,15 @@ class PreviewSession {
     // key R pressed (one render per press): Screen::requestRender -- a layer at the
     // camera (the RayTracer accumulates while the camera stays put), then updateScreen
     void pressRender();
+    // This build: with temporal on, R renders through RayTracer::rayTraceTemporal -- a layer at the camera merged with
+    // the reprojected history of the earlier presses, so a move, look or scroll keeps the samples taken so far
+    // instead of restarting at layer 1 (a camera that stays put accumulates through the same path).  Off (the
+    // default) is the reference's behaviour; switching drops the history.
+    void setTemporal(bool on) {
+        if (on != temporal_) renderer.resetTemporal();
+        temporal_ = on;
+    }
+    bool temporal() const { return temporal_; }
     // keys = / -: exposure +- 0.2, re-normalise the last render (no new layer)
     void exposureUp();
     void exposureDown();
@@ -55,6 +64,7 @@ class PreviewSession {
   private:
     Scene &scene;
     RayTracer &renderer;
+    bool temporal_ = false;
 };
 
 } // namespace chiaro

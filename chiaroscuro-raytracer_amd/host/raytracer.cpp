@@ -282,6 +282,63 @@ void RayTracer::denoise(unsigned levels, float sigmaL, float sigmaZ, float sigma
     showDenoised_ = true;
 }
 
+uint32_t RayTracer::rayTraceTemporal(vec3 eye, vec3 center, vec3 up, float yview, unsigned layers,
+                                     unsigned denoiseLevels) {
+    if (group_) throw std::runtime_error("chiaro: rayTraceTemporal renders on one GPU (gpus 1)");
+    if (layers < 1) throw std::runtime_error("chiaro: rayTraceTemporal: layers must be >= 1");
+    const auto t0 = std::chrono::high_resolution_clock::now();
+    const cr_camera cam = make_camera(eye, center, up, yview, scene.xres, scene.yres);
+    cr_render_params p{};
+    p.xres = scene.xres;
+    p.yres = scene.yres;
+    p.spp = scene.samples;
+    p.k = scene.k;
+    p.background[0] = scene.background.x;
+    p.background[1] = scene.background.y;
+    p.background[2] = scene.background.z;
+    p.seed = scene.seed + temporalFrames_;
+    p.layer = 1;
+    p.rank = 0;
+    p.nranks = 1;
+    p.tile = 32;
+    cr_temporal_params tp;
+    cr_temporal_params_default(&tp);
+    cr_denoise_params dp;
+    cr_denoise_params_default(&dp);
+    dp.levels = denoiseLevels;
+    // the frame is no progressive state, before or after: whatever follows starts at layer 1
+    layers_ = 0;
+    noiseTracked_ = false;
+    mixedLayers_ = false;
+    showDenoised_ = false;
+    lastEye = lastCenter = lastUp = vec3(FLT_MAX);
+    lastYview = -1;
+    denoised_.resize(pixels.size());
+    countMap_.assign((size_t)scene.xres * scene.yres, 0u);
+    if (cr_render_temporal(ctx_, &cam, &p, layers, &tp, denoiseLevels ? &dp : nullptr, denoised_.data(),
+                           countMap_.data()) != CR_OK) {
+        countMap_.clear();
+        throw std::runtime_error(std::string("chiaro: render failed: ") + cr_last_error(ctx_));
+    }
+    temporalFrames_++;
+    showDenoised_ = true;
+    cr_get_counters(ctx_, &counters_);
+    maxVal = 0.f;
+    for (float v : denoised_) maxVal = maxVal > v ? maxVal : v;
+    uint32_t least = 0;
+    for (uint32_t k : countMap_)
+        if (k && (!least || k < least)) least = k;
+    lastSeconds_ = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
+    return least;
+}
+
+void RayTracer::resetTemporal() {
+    if (group_) return; // (no history with gpus > 1)
+    if (cr_temporal_reset(ctx_) != CR_OK)
+        throw std::runtime_error(std::string("chiaro: temporal reset failed: ") + cr_last_error(ctx_));
+    temporalFrames_ = 0;
+}
+
 std::vector<float> RayTracer::noiseMap() {
     if (!noiseTracked_) throw std::runtime_error("chiaro: noiseMap: the frame is not a rayTraceUntil render");
     std::vector<float> err((size_t)scene.xres * scene.yres);

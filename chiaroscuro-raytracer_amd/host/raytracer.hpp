@@ -66,6 +66,17 @@ class RayTracer {
     void denoise(unsigned levels = 4, float sigmaL = 4.f, float sigmaZ = .1f, float sigmaA = .1f,
                  unsigned normalSquarings = 5);
     const float *denoisedData() const { return showDenoised_ ? denoised_.data() : nullptr; } // [yres][xres][3]
+    /* This build: temporal reprojection (cr_render_temporal, include/chiaro_hip.h "temporal reprojection"): `layers`
+     * layers at this view, merged with the history the earlier rayTraceTemporal calls left, carried to this camera
+     * through each pixel's first hit.  The seed is scene.seed plus the number of calls since the history began;
+     * denoiseLevels > 0 filters the shown frame with that many a-trous levels (the history stays unfiltered).  The
+     * result fills the denoised buffer: exportImage, normalizeImage and getData act on it until the next rayTrace*
+     * call.  The frame is no progressive state: the next rayTrace / rayTraceLayers / rayTraceUntil starts at layer 1.
+     * Returns the smallest non-zero sample count of the frame (countMap()).  One GPU only. */
+    uint32_t rayTraceTemporal(vec3 eye, vec3 center, vec3 up = vec3(0.f, 1.f, 0.f), float yview = 1.f,
+                              unsigned layers = 1, unsigned denoiseLevels = 0);
+    void resetTemporal(); // the next rayTraceTemporal starts a new history (and the seed again at scene.seed)
+    const std::vector<uint32_t> &countMap() const { return countMap_; } // [yres][xres]; empty before rayTraceTemporal
     /* The statistic of the last rayTraceUntil's last check, and the error map [yres][xres] of its frame. */
     const cr_noise_stats &lastNoise() const { return noise_; }
     std::vector<float> noiseMap();
@@ -108,7 +119,9 @@ class RayTracer {
     bool mixedLayers_ = false; // the frame is rayTraceAdaptive's: its pixels hold different layer counts
     cr_camera momentCam_{};    // the camera of the last rayTraceUntil / rayTraceAdaptive (denoise's guides)
     std::vector<float> denoised_;
-    bool showDenoised_ = false; // denoise() ran on this frame: export / normalize / getData act on denoised_
+    bool showDenoised_ = false; // denoise() / rayTraceTemporal() ran on this frame: export / normalize / getData act on denoised_
+    std::vector<uint32_t> countMap_;
+    uint32_t temporalFrames_ = 0; // rayTraceTemporal calls since the history began: the next call's seed offset
     const std::vector<float> &shown() const { return showDenoised_ ? denoised_ : pixels; }
     double lastSeconds_ = 0.0;
     // rayTracer.cpp:18-22 progressive-layer state (per instance here, not function-static)

@@ -46,6 +46,9 @@
  *   cr_guides_device / cr_guides / cr_denoise_device / cr_denoise
  *                        the albedo, normal and depth of each pixel's first hit, and a variance-guided a-trous filter
  *                        over the frame that uses them (no reference counterpart: its frame is the samples' mean, :59-64).
+ *   cr_reproject_device / cr_render_temporal / cr_temporal_reset / cr_temporal_history
+ *                        a frame's history carried to a moved camera through those guides and merged with the new
+ *                        samples (no reference counterpart: a changed view restarts its accumulation, :24-33).
  *   cr_intersect         KDTree::intersectRay       (src/kdtree.cpp:210-216)
  *   cr_intersect_shadow  KDTree::intersectShadowRay (src/kdtree.cpp:283-290)
  *   cr_intersect_device / cr_intersect_shadow_device
@@ -476,7 +479,7 @@ int cr_render_adaptive(cr_ctx *ctx, const cr_camera *cam, const cr_render_params
  * Errors: CR_E_INVALID (checked before the device) for a null pointer, levels > 8, normal_squarings > 8, a sigma not
  * finite or <= 0, xres or yres 0, layers * spp == 0 or above 32 bits; cr_denoise also for accumulators of another
  * size (after the device and scene checks).
- * Not covered: albedo demodulation (directly visible emitters break it), temporal reprojection, MODE_TILES,
+ * Not covered: albedo demodulation (directly visible emitters break it), MODE_TILES,
  * cr_group_*, cr_comm_* and the distributed renders; the checkpoint format is unchanged. */
 typedef struct cr_denoise_params {
     uint32_t levels;            /* a-trous iterations, 0..8; level i uses step 1 << i */
@@ -498,6 +501,79 @@ int cr_denoise_device(cr_ctx *ctx, uint32_t xres, uint32_t yres, uint32_t layers
                       float *d_var_out, void *stream);
 int cr_denoise(cr_ctx *ctx, const cr_camera *cam, uint32_t xres, uint32_t yres, uint32_t layers, uint32_t spp,
                const cr_denoise_params *dp, const uint32_t *layer_map, float *out, float *var_out);
+
+/* ------------------------------------------------------ temporal reprojection --
+ * A frame's samples kept when the camera moves: the history of the previous camera -- a frame H, a moment frame H2, a
+ * per-pixel sample count K and the guides Np (normal), Zp (depth) of its first hits -- is carried to the current
+ * camera through each pixel's first hit and merged with the current samples.  The other half of what the a-trous
+ * filter was taken from; like it, a definition of this build.
+ *
+ * float32, round to nearest, no contraction, IEEE division; operations in the order written.
+ *   cross(a, b) = (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z, a.x*b.y - a.y*b.x);  dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z
+ * PROJECTOR of the previous camera (eye_p, lu_p, dx_p, dy_p), on the host, once per call:
+ *   ra = cross(dx_p, dy_p);  rb = cross(dy_p, lu_p);  rc = cross(lu_p, dx_p);  det = dot(lu_p, ra)
+ *   det not finite or 0: CR_E_INVALID.
+ * PER PIXEL (x, y) of the current frame (C, M its frame and moment frame, Nc, Zc its guides, camera eye_c, lu_c, dx_c,
+ * dy_c), n_u its sample count as a uint32_t: layers * spp, with a layer map map * spp, wrapping (as cr_denoise_device
+ * forms its n):
+ *   1. not Zc >= 0 (a miss, or NaN): no history, h = 0.
+ *   2. sx = (float)x + 0.5f, sy = (float)y + 0.5f;  d = (lu_c + dx_c*sx) + dy_c*sy;  P = eye_c + d*Zc;  q = P - eye_p
+ *      a = dot(q, ra), b = dot(q, rb), c = dot(q, rc);  u = b / a, v = c / a
+ *      ze = a / det -- the depth the previous frame should hold there, in units of its direction; not ze > 0: h = 0.
+ *   3. fx = u - 0.5f, fy = v - 0.5f;  x0 = floorf(fx), y0 = floorf(fy);  wx = fx - x0, wy = fy - y0
+ *      taps (i, j) in the order (0,0), (1,0), (0,1), (1,1) at tx = x0 + (float)i, ty = y0 + (float)j, with the weights
+ *      (1-wx)*(1-wy), wx*(1-wy), (1-wx)*wy, wx*wy.
+ *   4. a tap q counts only if all of: 0 <= tx < (float)xres and 0 <= ty < (float)yres (compared in float before any
+ *      integer conversion: NaN and infinity fail);  K_q > 0;  Zp_q >= 0;  |Zp_q - ze| <= depth_tol * ze;
+ *      dot(Nc, Np_q) >= normal_min (a NaN fails);  no channel of H_q or H2_q is NaN;  its weight w > 0.
+ *   5. sums from 0 in tap order: sw = sw + w;  sr = sr + w*H_q, s2 = s2 + w*H2_q per channel;  kmin = min(kmin, K_q)
+ *   6. with at least one tap: R = sr / sw, R2 = s2 / sw, h = min(kmin, max_history); with none: h = 0.
+ *   7. the merge, hf = (float)h, nf = (float)n_u:
+ *        h == 0 and n_u > 0:  C, M, n_u -- the bits copied, no arithmetic
+ *        h > 0 and n_u == 0:  R, R2, h
+ *        both 0:              zeros and 0
+ *        otherwise:           tot = hf + nf;  out = (R*hf + C*nf) / tot per channel, m2_out likewise from R2 and M;
+ *                             count_out = min((uint64)h + n_u, 2^32 - 1)
+ * A disoccluded pixel (no tap passes) therefore is the current pixel bit for bit, and max_history bounds the weight of
+ * the past: with max_history = k the merge is an exponential average of weight k / (k + n_u) once the count reaches k.
+ *
+ * cr_reproject_device: all arrays device-resident, [yres][xres][3] floats for frames, moments and normals,
+ * [yres][xres] for depths (float) and counts / the layer map (uint32).  Stream-ordered, no host synchronisation, no
+ * scene needed, cr_get_counters untouched; d_layer_map may be null; outputs must not alias inputs.
+ * cr_render_temporal (p->layer 1, p->nranks 1): layers 1 .. nlayers with moments for cam into buffers of the ctx's
+ * temporal state -- the two progressive accumulators stay as they are --, the normal and depth guides, then the
+ * ctx's history (kept when it is of the same size) reprojected and merged; without one the history becomes the
+ * current frame with count nlayers * spp.  The result, the guides and cam are the new history (double-buffered).
+ * out [yres][xres][3] is the merged frame -- with dp not null cr_denoise_device's result on the merged frame and
+ * moments, the count map as d_layer_map and spp 1; the stored history stays unfiltered --, count_out (nullable)
+ * the merged counts.  p->seed is the caller's: successive frames need different seeds, or the same sample
+ * positions are drawn again and the merge averages correlated samples.  cr_temporal_reset drops the history;
+ * cr_temporal_history copies it out (any pointer may be null; CR_E_INVALID without a history).
+ * The scratch rules are the denoiser's: grow-only, a call on another stream than the last waits on the device, a
+ * regrow waits on the host.
+ * Errors: CR_E_INVALID (before the device) for a null required pointer, depth_tol not finite or <= 0, normal_min not
+ * finite, max_history 0, xres or yres 0, the degenerate projector; cr_render_temporal also for p->layer != 1,
+ * nranks != 1, nlayers 0 and dp's own errors; then the device (CR_E_HIP), then the scene (CR_E_NOSCENE).
+ * Not covered: background (miss) pixels carry no history; no albedo demodulation (texture detail blurs with the
+ * bilinear taps); one GPU, whole frames (no MODE_TILES, cr_group_*, cr_comm_*). */
+typedef struct cr_temporal_params {
+    float depth_tol;       /* relative depth difference a tap may have (> 0) */
+    float normal_min;      /* the least dot product of the two normals */
+    uint32_t max_history;  /* the history count is clamped to this (> 0) */
+} cr_temporal_params;
+void cr_temporal_params_default(cr_temporal_params *out); /* 0.05, 0.9, 65536 */
+/* sizeof the structure as this library was built */
+void cr_temporal_struct_sizes(uint32_t *params_bytes);
+int cr_reproject_device(cr_ctx *ctx, const cr_camera *cam_cur, const cr_camera *cam_prev, uint32_t xres, uint32_t yres,
+                        uint32_t layers, uint32_t spp, const cr_temporal_params *tp, const float *d_frame,
+                        const float *d_m2, const uint32_t *d_layer_map, const float *d_normal, const float *d_depth,
+                        const float *d_hist_frame, const float *d_hist_m2, const uint32_t *d_hist_count,
+                        const float *d_hist_normal, const float *d_hist_depth, float *d_out, float *d_m2_out,
+                        uint32_t *d_count_out, void *stream);
+int cr_render_temporal(cr_ctx *ctx, const cr_camera *cam, const cr_render_params *p, uint32_t nlayers,
+                       const cr_temporal_params *tp, const cr_denoise_params *dp, float *out, uint32_t *count_out);
+int cr_temporal_reset(cr_ctx *ctx);
+int cr_temporal_history(cr_ctx *ctx, float *frame, float *m2, uint32_t *count);
 
 /* Ray queries (host arrays). dir need not be normalised (the reference does not). */
 int cr_intersect(cr_ctx *ctx, uint32_t n, const float *orig, const float *dir, uint32_t *hit, uint32_t *tri,

@@ -13,6 +13,8 @@
  *                            build; cr_render_adaptive)
  *   chiaro_raytracer_denoise / _denoised
  *                            an edge-avoiding filter over such a frame (this build; cr_denoise)
+ *   chiaro_raytracer_raytrace_temporal / _reset_temporal / _count_map, chiaro_preview_set_temporal
+ *                            a frame's history carried to a moved camera (this build; cr_render_temporal)
  *   chiaro_raytracer_raytrace_until / _noise / _noise_map
  *                            rayTrace repeated until a noise target is met (this build; the accumulation of
  *                            src/rayTracer.cpp:18-33,59-64 with a second-moment frame, cr_render_until)
@@ -125,6 +127,18 @@ int chiaro_raytracer_layer_map(const chiaro_raytracer *r, uint32_t *layers_out);
 int chiaro_raytracer_denoise(chiaro_raytracer *r, uint32_t levels, float sigma_l, float sigma_z, float sigma_a,
                              uint32_t normal_squarings);
 const float *chiaro_raytracer_denoised(const chiaro_raytracer *r);
+/* RayTracer::rayTraceTemporal: `layers` layers at this view merged with the history the earlier calls left, carried
+ * to this camera through each pixel's first hit (cr_render_temporal, include/chiaro_hip.h "temporal reprojection");
+ * the seed advances by one per call.  denoise_levels > 0: the shown frame is filtered with that many a-trous levels.
+ * chiaro_raytracer_data / _normalize / _export / _denoised act on the result until the next raytrace call, which
+ * starts at layer 1.  *min_count_out (may be NULL): the smallest non-zero sample count of the frame.  One GPU only.
+ * chiaro_raytracer_reset_temporal drops the history; chiaro_raytracer_count_map: each pixel's sample count, uint32
+ * [yres][xres] (CR_E_INVALID before the first temporal render). */
+int chiaro_raytracer_raytrace_temporal(chiaro_raytracer *r, const float eye[3], const float center[3],
+                                       const float up[3], float yview, uint32_t layers, uint32_t denoise_levels,
+                                       uint32_t *min_count_out);
+int chiaro_raytracer_reset_temporal(chiaro_raytracer *r);
+int chiaro_raytracer_count_map(const chiaro_raytracer *r, uint32_t *counts_out);
 const float *chiaro_raytracer_pixels(const chiaro_raytracer *r);
 const uint8_t *chiaro_raytracer_data(chiaro_raytracer *r);
 float chiaro_raytracer_maxval(const chiaro_raytracer *r);
@@ -183,6 +197,9 @@ enum {
 chiaro_preview *chiaro_preview_create(chiaro_scene *s, chiaro_raytracer *r);
 /* one key press; dt = frame time for the movement keys, shift = LEFT_SHIFT held */
 int chiaro_preview_key(chiaro_preview *p, int key, float dt, int shift);
+/* on != 0: key R renders through chiaro_raytracer_raytrace_temporal, so a moved camera keeps the samples taken so far
+ * instead of restarting at layer 1; 0 (the default): the reference's behaviour.  A change drops the history. */
+int chiaro_preview_set_temporal(chiaro_preview *p, int on);
 int chiaro_preview_mouse(chiaro_preview *p, float xoffset, float yoffset);
 int chiaro_preview_scroll(chiaro_preview *p, float yoffset);
 /* the screen texture (RayTracer::getData after normalizeImage), width x height x RGB8 */
