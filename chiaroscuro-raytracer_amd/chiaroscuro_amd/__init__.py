@@ -223,6 +223,17 @@ class CrTemporalParams(C.Structure):
     _fields_ = [("depth_tol", C.c_float), ("normal_min", C.c_float), ("max_history", C.c_uint32)]
 
 
+class CrRadianceParams(C.Structure):
+    """cr_radiance_params (include/chiaro_hip.h "radiance queries")."""
+    _fields_ = [("spp", C.c_uint32), ("k", C.c_int32), ("background", C.c_float * 3), ("seed", C.c_uint32),
+                ("layer", C.c_uint32), ("id0", C.c_uint32)]
+
+
+def radiance_params(spp, k, seed, background=(0.0, 0.0, 0.0), layer=1, id0=0) -> CrRadianceParams:
+    return CrRadianceParams(int(spp), int(k), (C.c_float * 3)(*[float(v) for v in background]), int(seed) & 0xffffffff,
+                            int(layer), int(id0))
+
+
 def temporal_params(depth_tol=None, normal_min=None, max_history=None) -> CrTemporalParams:
     """cr_temporal_params_default (0.05, 0.9, 65536) with the given fields replaced."""
     tp = CrTemporalParams()
@@ -263,7 +274,8 @@ HIP_SYMBOLS = ("cr_create", "cr_destroy", "cr_last_error", "cr_upload_scene", "c
                "cr_denoise_params_default", "cr_denoise_struct_sizes", "cr_guides_device", "cr_guides",
                "cr_denoise_device", "cr_denoise",
                "cr_temporal_params_default", "cr_temporal_struct_sizes", "cr_reproject_device", "cr_render_temporal",
-               "cr_temporal_reset", "cr_temporal_history")
+               "cr_temporal_reset", "cr_temporal_history",
+               "cr_radiance_struct_sizes", "cr_radiance_device", "cr_gather_device", "cr_radiance", "cr_gather")
 HOST_SYMBOLS = ("chiaro_last_error", "chiaro_scene_create", "chiaro_scene_info_get", "chiaro_scene_destroy",
                 "chiaro_model_create", "chiaro_model_load", "chiaro_model_num_meshes", "chiaro_model_num_triangles",
                 "chiaro_model_num_textures", "chiaro_model_triangles", "chiaro_model_texture",
@@ -283,7 +295,8 @@ HOST_SYMBOLS = ("chiaro_last_error", "chiaro_scene_create", "chiaro_scene_info_g
                 "chiaro_raytracer_noise_map", "chiaro_noise_struct_sizes", "chiaro_raytracer_raytrace_adaptive",
                 "chiaro_raytracer_adaptive", "chiaro_raytracer_layer_map", "chiaro_raytracer_denoise",
                 "chiaro_raytracer_denoised", "chiaro_raytracer_raytrace_temporal", "chiaro_raytracer_reset_temporal",
-                "chiaro_raytracer_count_map", "chiaro_preview_set_temporal")
+                "chiaro_raytracer_count_map", "chiaro_preview_set_temporal", "chiaro_raytracer_radiance",
+                "chiaro_raytracer_gather")
 
 P = C.c_void_p
 FP = C.POINTER(C.c_float)
@@ -419,6 +432,12 @@ def libs():
          [CTX, C.POINTER(CrCamera), C.POINTER(CrRenderParams), C.c_uint32, TP, DP, FP, UP])
     _sig(hip, "cr_temporal_reset", C.c_int, [CTX])
     _sig(hip, "cr_temporal_history", C.c_int, [CTX, FP, FP, UP])
+    RP = C.POINTER(CrRadianceParams)
+    _sig(hip, "cr_radiance_struct_sizes", None, [UP])
+    for name in ("cr_radiance_device", "cr_gather_device"):
+        _sig(hip, name, C.c_int, [CTX, C.c_uint32, P, P, RP, C.c_uint32, P, P, P])
+    for name in ("cr_radiance", "cr_gather"):
+        _sig(hip, name, C.c_int, [CTX, C.c_uint32, FP, FP, RP, C.c_uint32, FP, FP])
 
     _sig(host, "chiaro_last_error", C.c_char_p, [])
     _sig(host, "chiaro_scene_create", P, [C.c_int, C.POINTER(C.c_char_p)])
@@ -458,6 +477,8 @@ def libs():
     _sig(host, "chiaro_raytracer_reset_temporal", C.c_int, [P])
     _sig(host, "chiaro_raytracer_count_map", C.c_int, [P, UP])
     _sig(host, "chiaro_preview_set_temporal", C.c_int, [P, C.c_int])
+    _sig(host, "chiaro_raytracer_radiance", C.c_int, [P, FP, FP, C.c_uint32, C.c_uint32, FP])
+    _sig(host, "chiaro_raytracer_gather", C.c_int, [P, FP, FP, C.c_uint32, C.c_uint32, FP])
     _sig(host, "chiaro_raytracer_pixels", FP, [P])
     _sig(host, "chiaro_raytracer_data", C.POINTER(C.c_uint8), [P])
     _sig(host, "chiaro_raytracer_maxval", C.c_float, [P])
@@ -927,6 +948,46 @@ class Device:
                                                 C.c_void_p(d_bary_ptr or None), C.c_void_p(d_dist_ptr or None),
                                                 C.c_void_p(stream)), "cr_intersect_device")
 
+    def radiance_device(self, n: int, d_orig_ptr: int, d_dir_ptr: int, rp: CrRadianceParams, nlayers: int,
+                        d_out_ptr: int, d_m2_ptr: int = 0, stream: int = 0):
+        """cr_radiance_device: layers rp.layer .. + nlayers - 1 of the path-traced radiance along n device rays
+        ([n][3] float origins / directions, not normalised; ray i draws from stream rp.id0 + i), blended into the
+        device arrays d_out [n][3] and, when given, d_m2 [n][3] as a frame pixel is.  Returns when complete."""
+        self._chk(libs()[0].cr_radiance_device(self._c, int(n), C.c_void_p(d_orig_ptr or None),
+                                               C.c_void_p(d_dir_ptr or None), C.byref(rp), int(nlayers),
+                                               C.c_void_p(d_out_ptr or None), C.c_void_p(d_m2_ptr or None),
+                                               C.c_void_p(stream)), "cr_radiance_device")
+
+    def gather_device(self, n: int, d_pos_ptr: int, d_nrm_ptr: int, rp: CrRadianceParams, nlayers: int,
+                      d_out_ptr: int, d_m2_ptr: int = 0, stream: int = 0):
+        """cr_gather_device: the mean incoming radiance under the cosine density at n device points ([n][3] float
+        positions / normals); irradiance is pi times it.  Outputs as radiance_device's."""
+        self._chk(libs()[0].cr_gather_device(self._c, int(n), C.c_void_p(d_pos_ptr or None),
+                                             C.c_void_p(d_nrm_ptr or None), C.byref(rp), int(nlayers),
+                                             C.c_void_p(d_out_ptr or None), C.c_void_p(d_m2_ptr or None),
+                                             C.c_void_p(stream)), "cr_gather_device")
+
+    def _radiance_host(self, fn, name, a, b, rp, nlayers, out, m2):
+        a = np.ascontiguousarray(a, np.float32).reshape(-1, 3)
+        b = np.ascontiguousarray(b, np.float32).reshape(-1, 3)
+        n = len(a)
+        assert len(b) == n
+        out = np.zeros((n, 3), np.float32) if out is None else out
+        assert out.dtype == np.float32 and out.flags.c_contiguous and out.size == 3 * n
+        if m2 is not None:
+            assert m2.dtype == np.float32 and m2.flags.c_contiguous and m2.size == 3 * n
+        self._chk(fn(self._c, n, _ptr(a), _ptr(b), C.byref(rp), int(nlayers), _ptr(out),
+                     _ptr(m2) if m2 is not None else None), name)
+        return out
+
+    def radiance(self, orig, dirs, rp: CrRadianceParams, nlayers: int = 1, out=None, m2=None) -> np.ndarray:
+        """cr_radiance on host arrays; out / m2 ([n][3] float32) are read for rp.layer > 1 and written."""
+        return self._radiance_host(libs()[0].cr_radiance, "cr_radiance", orig, dirs, rp, nlayers, out, m2)
+
+    def gather(self, pos, nrm, rp: CrRadianceParams, nlayers: int = 1, out=None, m2=None) -> np.ndarray:
+        """cr_gather on host arrays (see gather_device)."""
+        return self._radiance_host(libs()[0].cr_gather, "cr_gather", pos, nrm, rp, nlayers, out, m2)
+
     def intersect_shadow_device(self, n: int, d_orig_ptr: int, d_dir_ptr: int, d_dist_ptr: int, d_light_ptr: int,
                                 d_occluded_ptr: int, stream: int = 0):
         """cr_intersect_shadow_device: n shadow queries on device arrays, enqueued on `stream`."""
@@ -1236,6 +1297,25 @@ class RayTracer:
         if rc:
             raise RuntimeError("rayTraceTemporal: " + _host_err())
         return int(least.value)
+
+    def _radiance(self, fn, name, a, b, layers):
+        a = np.ascontiguousarray(a, np.float32).reshape(-1, 3)
+        b = np.ascontiguousarray(b, np.float32).reshape(-1, 3)
+        assert len(a) == len(b)
+        out = np.zeros((len(a), 3), np.float32)
+        if fn(self._h, _ptr(a), _ptr(b), len(a), int(layers), _ptr(out)):
+            raise RuntimeError(name + ": " + _host_err())
+        return out
+
+    def radiance(self, orig, dirs, layers=1) -> np.ndarray:
+        """The path-traced light along the rays (orig, dirs: [n][3], dirs not normalised): layers 1 .. layers with the
+        Scene's samples, k, background and seed (cr_radiance); [n][3].  The frame is untouched."""
+        return self._radiance(libs()[1].chiaro_raytracer_radiance, "radiance", orig, dirs, layers)
+
+    def gather(self, pos, nrm, layers=1) -> np.ndarray:
+        """The mean incoming radiance under the cosine density at the points (pos, nrm: [n][3]); irradiance is pi
+        times it, and offsetting pos off the surface is the caller's job (cr_gather); [n][3]."""
+        return self._radiance(libs()[1].chiaro_raytracer_gather, "gather", pos, nrm, layers)
 
     def resetTemporal(self):
         if libs()[1].chiaro_raytracer_reset_temporal(self._h):

@@ -6,6 +6,7 @@
 #include "ctx.hpp"
 #include "adaptive.hpp"
 #include "denoise.hpp"
+#include "radiance.hpp"
 #include "scenelayout.hpp"
 #include "temporal.hpp"
 #include "wfplan.hpp"
@@ -195,8 +196,10 @@ cr_counters counters_of(const unsigned long long *h) {
 
 int run_render(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, float *out, int mode, hipStream_t st,
                uint32_t nl, uint32_t piece_k, uint32_t piece_m, uint64_t stride, float *m2, const uint32_t *list,
-               uint32_t list_items) {
+               uint32_t list_items, const cr::RaySrc *rays) {
     if (!cam || !out) return fail(c, CR_E_INVALID, "null camera/output");
+    if (rays && (!list || c->kernel != 2 || c->perf_counters))
+        return fail(c, CR_E_INVALID, "a ray pass is a list pass of the wavefront kernel, without perf_counters");
     if (m2 && mode != cr::MODE_BLEND) return fail(c, CR_E_INVALID, "moments are tracked for blended frames only");
     int rc = check_params(c, p);
     if (rc) return rc;
@@ -254,11 +257,15 @@ int run_render(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, float
     // a list pass runs the unfused camera path, whatever the options say: wf_camera_list makes the rays and writes
     // generation 1's RNG state, and no trace, shade, resolve or tail kernel then derives a pixel from a work item
     if (list) W.cam_fused = W.cam_lean = W.ctl_ray = W2.cam_fused = W2.cam_lean = W2.ctl_ray = 0;
+    // a ray pass: an item index says nothing about where a ray starts, so the queues that would
+    // take pixel keys take world keys from generation 1 on (when the plan sized the keys for them: option
+    // "wf_world_keys" not 0); leaf keys, where the scene has them, describe any ray and stay
+    if (rays && !W.leaf_keys && W.world_keys) W.world_keys = 1;
     // screen-space cull boxes of this camera for the camera-ray trace (camcull.hpp),
     // computed inside the timed region of every render
     // (built for triangle-less scenes too: the culling kernels read them unconditionally, and
     // with n_refs + 4 empty boxes every sample is outside)
-    const bool cull = !c->full_counters && cr::wf_variant_culls(A.variant);
+    const bool cull = !rays && !c->full_counters && cr::wf_variant_culls(A.variant); // (a ray pass has no camera)
     if (cull) {
         if (int r = grow(c, c->d_cull, 16 * ((size_t)c->n_refs + 4))) return r;
         if (int r = grow(c, c->d_cull_node, 16 * (size_t)c->S.n_nodes)) return r;
@@ -278,7 +285,7 @@ int run_render(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, float
         A.s_count = (uint32_t)std::min<uint64_t>(pl.chunk, pl.spp_pass - s0);
         A.n_work = A.n_items * A.s_count;
         int e = 0;
-        if (lanes == 2) {
+        if (lanes == 2 && !rays) {
             cr::WfLane L[2] = {{W, st, c->side, c->fork, c->join, c->lane_ev[0], c->hcnt.words()},
                                {W2, c->stream2, c->side2, c->fork2, c->join2, c->lane_ev[1], c->hcnt.words() + 2}};
             e = cr::run_wavefront_lanes(A, L, 2, c->num_cus, st, &c->tev);
@@ -288,7 +295,7 @@ int run_render(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, float
                 W.w0 = w0;
                 W.P = std::min(P, A.n_work - w0);
                 HIPCHK(hipMemsetAsync(W.cnt, 0, cr::WF_CNT * sizeof(uint32_t), st));
-                e = cr::launch_wavefront_chunk(A, W, c->num_cus, st, wfs, &c->tev);
+                e = cr::launch_wavefront_chunk(A, W, c->num_cus, st, wfs, &c->tev, rays);
             }
             W.P = P;
         }
@@ -1180,6 +1187,95 @@ int cr_render_layers_list_device(cr_ctx *c, const cr_camera *cam, const cr_rende
     if (int rc = render_list(c, cam, q, nlayers, d_list, n_list, d_frame, d_m2, (hipStream_t)stream, sum)) return rc;
     sum.store(c);
     return CR_OK;
+}
+
+// ---- radiance queries ----
+void cr_radiance_struct_sizes(uint32_t *params_bytes) {
+    if (params_bytes) *params_bytes = (uint32_t)sizeof(cr_radiance_params);
+}
+// The arguments of the four entries (radiance.hpp rad_check), then the device, then the scene
+static int radiance_enter(cr_ctx *c, uint32_t n, const void *a, const void *b, const cr_radiance_params *p,
+                          uint32_t nlayers, const void *out) {
+    if (!c) return CR_E_INVALID;
+    if (const char *msg = cr::rad_check(n, a && b && out, p != nullptr, p ? p->spp : 0, p ? p->k : 0, p ? p->layer : 0,
+                                        p ? p->id0 : 0, nlayers))
+        return fail(c, CR_E_INVALID, msg);
+    if (int rc = enter(c)) return rc;
+    if (!c->has_scene) return fail(c, CR_E_NOSCENE, "no scene uploaded");
+    return CR_OK;
+}
+// Layers p->layer .. + nlayers - 1 of n rays (a, b) blended into d_out (and d_m2), as the ray passes of ad_plan: each
+// pass is a list pass over the identity list of its batch, an n x 1 frame at the batch's offset into the outputs.
+static int run_radiance(cr_ctx *c, uint32_t n, const float *d_a, const float *d_b, bool gather,
+                        const cr_radiance_params *p, uint32_t nlayers, float *d_out, float *d_m2, hipStream_t st) {
+    const uint32_t max_nl = c->kernel != 2 || c->wf_lanes != 1 || c->full_counters ? 1u : 32u; // (cr_layers_per_pass's rule)
+    const cr::AdPlanIn in = cr::rad_plan_in(n, nlayers, p->spp, max_nl, std::min<uint64_t>(c->wf_paths, wf_path_cap(c, p->k)),
+                                            c->sample_buf);
+    const cr_camera cam{}; // (no kernel of a ray pass reads a camera)
+    PassTotals sum;
+    for (const cr::AdPass &ap : cr::ad_plan(in)) {
+        const cr::RadPass ps = cr::rad_pass(ap, in.tile, p->id0, p->layer);
+        if (int r = grow(c, c->d_list_pad, (size_t)ps.items * sizeof(uint32_t))) return r;
+        if (int e = cr::launch_ray_list(c->d_list_pad.as<uint32_t>(), ps.count, ps.items, st))
+            return hip_fail(c, (hipError_t)e, "ray list kernel launch");
+        cr_render_params t{};
+        t.xres = ps.count, t.yres = 1, t.spp = p->spp, t.k = p->k;
+        std::memcpy(t.background, p->background, sizeof t.background);
+        t.seed = p->seed, t.layer = ps.layer, t.rank = 0, t.nranks = 1, t.tile = in.tile;
+        const cr::RaySrc src{d_a + 3 * (size_t)ps.first, d_b + 3 * (size_t)ps.first, ps.id0, gather ? 1 : 0};
+        if (int rc = crx::run_render(c, &cam, &t, d_out + 3 * (size_t)ps.first, cr::MODE_BLEND, st, ps.nl, 0, 1, 0,
+                                     d_m2 ? d_m2 + 3 * (size_t)ps.first : nullptr, c->d_list_pad.as<uint32_t>(), ps.items,
+                                     &src))
+            return rc;
+        sum.add(c);
+    }
+    sum.store(c);
+    return CR_OK;
+}
+static int radiance_device(cr_ctx *c, uint32_t n, const float *d_a, const float *d_b, bool gather,
+                           const cr_radiance_params *p, uint32_t nlayers, float *d_out, float *d_m2, void *stream) {
+    if (int rc = radiance_enter(c, n, d_a, d_b, p, nlayers, d_out)) return rc;
+    if (n == 0) return CR_OK;
+    return run_radiance(c, n, d_a, d_b, gather, p, nlayers, d_out, d_m2, (hipStream_t)stream);
+}
+// the host forms: the arrays through scoped device buffers, on the ctx's stream
+static int radiance_host(cr_ctx *c, uint32_t n, const float *a, const float *b, bool gather, const cr_radiance_params *p,
+                         uint32_t nlayers, float *out, float *m2) {
+    if (int rc = radiance_enter(c, n, a, b, p, nlayers, out)) return rc;
+    if (n == 0) return CR_OK;
+    const size_t bytes = (size_t)n * 3 * sizeof(float);
+    DevBuf d_a, d_b, d_o, d_m;
+    if (int r = grow(c, d_a, bytes, "radiance inputs")) return r;
+    if (int r = grow(c, d_b, bytes, "radiance inputs")) return r;
+    if (int r = grow(c, d_o, bytes, "radiance outputs")) return r;
+    if (m2)
+        if (int r = grow(c, d_m, bytes, "radiance outputs")) return r;
+    HIPCHK(hipMemcpy(d_a.ptr, a, bytes, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_b.ptr, b, bytes, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_o.ptr, out, bytes, hipMemcpyHostToDevice)); // (layer > 1 blends onto the caller's values)
+    if (m2) HIPCHK(hipMemcpy(d_m.ptr, m2, bytes, hipMemcpyHostToDevice));
+    if (int rc = run_radiance(c, n, d_a.as<float>(), d_b.as<float>(), gather, p, nlayers, d_o.as<float>(),
+                              m2 ? d_m.as<float>() : nullptr, c->stream))
+        return rc;
+    HIPCHK(hipMemcpy(out, d_o.ptr, bytes, hipMemcpyDeviceToHost));
+    if (m2) HIPCHK(hipMemcpy(m2, d_m.ptr, bytes, hipMemcpyDeviceToHost));
+    return CR_OK;
+}
+int cr_radiance_device(cr_ctx *c, uint32_t n, const float *d_orig, const float *d_dir, const cr_radiance_params *p,
+                       uint32_t nlayers, float *d_out, float *d_m2, void *stream) {
+    return radiance_device(c, n, d_orig, d_dir, false, p, nlayers, d_out, d_m2, stream);
+}
+int cr_gather_device(cr_ctx *c, uint32_t n, const float *d_pos, const float *d_nrm, const cr_radiance_params *p,
+                     uint32_t nlayers, float *d_out, float *d_m2, void *stream) {
+    return radiance_device(c, n, d_pos, d_nrm, true, p, nlayers, d_out, d_m2, stream);
+}
+int cr_radiance(cr_ctx *c, uint32_t n, const float *orig, const float *dir, const cr_radiance_params *p,
+                uint32_t nlayers, float *out, float *m2) {
+    return radiance_host(c, n, orig, dir, false, p, nlayers, out, m2);
+}
+int cr_gather(cr_ctx *c, uint32_t n, const float *pos, const float *nrm, const cr_radiance_params *p, uint32_t nlayers,
+              float *out, float *m2) {
+    return radiance_host(c, n, pos, nrm, true, p, nlayers, out, m2);
 }
 
 int cr_noise_select_device(cr_ctx *c, uint32_t xres, uint32_t yres, uint32_t layers, uint32_t spp,

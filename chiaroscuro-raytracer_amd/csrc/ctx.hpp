@@ -130,7 +130,8 @@ cr::BlendArgs blend_args(const cr_render_params *p, const float *gathered, float
 // (RenderArgs::list; a multiple of tile * tile, padded with skipped entries), not p's tiles
 int run_render(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, float *out, int mode, hipStream_t st,
                uint32_t nl = 1, uint32_t piece_k = 0, uint32_t piece_m = 1, uint64_t stride = 0,
-               float *m2 = nullptr, const uint32_t *list = nullptr, uint32_t list_items = 0);
+               float *m2 = nullptr, const uint32_t *list = nullptr, uint32_t list_items = 0,
+               const cr::RaySrc *rays = nullptr);
 // group.cpp: the communicator and buffers of the multi-process split (cr_destroy)
 void release_dist(cr_ctx *c);
 // The largest nl <= want (>= 1) whose paths fit one chunk when p's share (the frame for nranks 1, else rank

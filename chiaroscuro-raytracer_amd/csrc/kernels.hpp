@@ -450,8 +450,18 @@ struct WfLane {
 };
 int run_wavefront_lanes(const RenderArgs &A, WfLane *lanes, int nlanes, int num_cus, hipStream_t st,
                         TraceEvents *te);
+// A ray pass (cr_radiance_device / cr_gather_device): the first rays of the pass's paths are the
+// caller's.  The pass is a list pass over the identity list of its batch (launch_ray_list): entry e takes ray
+// (a[e], b[e]) -- origin and direction, or (gather) position and normal -- and RNG stream id id0 + e.  An argument of
+// the generation-0 kernel alone (wavefront.hip wf_camera_rays): RenderArgs and WfArgs keep their layout.
+struct RaySrc {
+    const float *a, *b; // [count][3] each, device
+    uint32_t id0;       // the stream id of entry 0
+    int gather;         // 1: a = positions, b = normals, the direction drawn about the normal
+};
+int launch_ray_list(uint32_t *list, uint32_t count, uint32_t n_items, hipStream_t st);
 int launch_wavefront_chunk(const RenderArgs &A, const WfArgs &W, int num_cus, hipStream_t st, const WfStreams &ss,
-                           TraceEvents *te = nullptr);
+                           TraceEvents *te = nullptr, const RaySrc *rays = nullptr);
 // raysort.hip: stable radix sort of (key, value) pairs; lib: hipcub's instead
 int sort_queue(uint32_t *keys[2], uint32_t *vals[2], uint32_t n, int end_bit, void *tmp, size_t &tmp_bytes,
                hipStream_t st, bool lib = false, bool iota = false, bool keep_keys = true);

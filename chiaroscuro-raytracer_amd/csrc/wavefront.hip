@@ -6,7 +6,8 @@
 // (2 -> 6 waves/SIMD: 260 -> 563 Mray/s).  Here the same per-path arithmetic is
 // split by phase into kernels that exchange work through queues in HBM:
 //
-//   wf_camera                 one closest ray per path of the chunk (wf_camera_list: of a list pass)
+//   wf_camera                 one closest ray per path of the chunk (wf_camera_list: of a list pass;
+//                             wf_camera_rays: of a ray pass, whose first rays are the caller's)
 //   wf_trace<closest>(1)
 //   for g = 1..K:
 //     wf_shade(g)             hit reconstruction, emission, NEE light sample
@@ -244,6 +245,62 @@ __device__ __forceinline__ void camera_rays(const RenderArgs &A, const WfArgs &W
 }
 __global__ void __launch_bounds__(256) wf_camera(RenderArgs A, WfArgs W) { camera_rays<false>(A, W); }
 __global__ void __launch_bounds__(256) wf_camera_list(RenderArgs A, WfArgs W) { camera_rays<true>(A, W); }
+
+// Generation 0 of a ray pass (cr_radiance_device / cr_gather_device): the paths' first rays are the
+// caller's, not a camera's.  Path p maps to (item, sample, layer) as in camera_rays<true>; the pass's list is the
+// identity over the batch's entries (padding: LIST_SKIP, a dead entry), so entry e = list[item] reads ray e of R and
+// draws from the render's stream (seed, layer, R.id0 + e, sample) -- keyed as pixel index R.id0 + e is -- with the
+// counter at 2, where a camera sample's stands after its two aim draws.
+// GATHER false: the ray is (a[e], b[e]) as given; the aim draws are skipped.
+// GATHER true: a = positions, b = normals; draws 0 and 1 aim the BRDF's cosine-weighted direction about the normal
+// (brdf_step's two rng_uniform and sample_wi; the pdf is not used).
+// The caller's arrays and the first id are this kernel's own argument: RenderArgs and WfArgs keep their layout.
+template <bool GATHER>
+__global__ void __launch_bounds__(256) wf_camera_rays(RenderArgs A, WfArgs W, RaySrc R) {
+    __shared__ unsigned long long tl[T_N];
+    if (threadIdx.x < T_N) tl[threadIdx.x] = 0;
+    __syncthreads();
+    for (uint32_t base = blockIdx.x * blockDim.x; base < W.P; base += gridDim.x * blockDim.x) {
+        const uint32_t p = base + threadIdx.x;
+        const uint32_t w = W.w0 + p;
+        uint32_t item = 0, s = 0, e = 0, ey = 0;
+        bool valid = p < W.P && w < A.n_work;
+        if (valid) {
+            item = w / A.s_count;
+            s = A.s0 + (w - item * A.s_count);
+            valid = item_pixel_of<true>(A, item, e, ey); // (a frame of n entries x 1: e is the entry)
+        }
+        tally(tl, T_PATHS, valid);
+        if (valid) {
+            Rng rng = path_rng(A, R.id0 + e, s);
+            const float *a = R.a + 3 * (size_t)e, *b = R.b + 3 * (size_t)e;
+            const f3 o = mk(a[0], a[1], a[2]);
+            f3 d = mk(b[0], b[1], b[2]);
+            if (GATHER) {
+                const float sx = rng_uniform(rng, -1.f, 1.f);
+                const float sy = rng_uniform(rng, -1.f, 1.f);
+                float pdf;
+                sample_wi(mk(b[0], b[1], b[2]), sx, sy, d, pdf);
+            } else {
+                rng.ctr = 2u;
+            }
+            ctl_store(W, p, 1u, rng);
+            W.mark[p] = 0; // no resolve mark (wf_resolve)
+            W.ray[1][2 * (size_t)p] = pk(o, p);
+            W.ray[1][2 * (size_t)p + 1] = pk(d, 0u);
+        } else if (p < W.P) {
+            W.mark[p] = 0;
+            dead_entry(W.ray[1], p);
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) *cnt_closest(W, 1) = W.P;
+    flush_tallies(A, tl);
+}
+// the identity list of a ray pass's batch: entry i for i < count, LIST_SKIP for the padding up to n_items
+__global__ void __launch_bounds__(256) ray_list_kernel(uint32_t *list, uint32_t count, uint32_t n_items) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_items) list[i] = i < count ? i : LIST_SKIP;
+}
 
 // The result of shadow query idx of generation g: occ[idx] or, with WfArgs::vis_dw, the w of the path's
 // dw record of bounce g (idx is then the path), which held the query's slot (SHADOW_VIS / SHADOW_OCC
@@ -1661,9 +1718,10 @@ struct ChunkLauncher {
     size_t lds = 0;
     uint32_t sgrid; // grid-stride phases
     int err = 0;
-    ChunkLauncher(const RenderArgs &A_, int num_cus_, TraceEvents *te_, const WfDriver &drv_)
+    const RaySrc *const rays; // a ray pass: generation 1 is the caller's rays, on the general closest trace
+    ChunkLauncher(const RenderArgs &A_, int num_cus_, TraceEvents *te_, const WfDriver &drv_, const RaySrc *rays_ = nullptr)
         : A(A_), num_cus(num_cus_), te(te_), drv(drv_), mode(wf_mode(A_.full_counters, A_.perf_counters)),
-          b(wf_render_build(A_.variant, mode)) {
+          b(wf_render_build(A_.variant, mode)), rays(rays_) {
         if (b) blocks = wf_trace_blocks(b->id, num_cus), lds = wf_ring_bytes(b->ring);
         sgrid = (uint32_t)(num_cus > 0 ? num_cus : 256) * 8;
     }
@@ -1695,9 +1753,23 @@ struct ChunkLauncher {
         WfArgs Wc = W;
         Wc.order = order;
         Wc.gstack = gstack;
+        if (g == 1 && rays) return first_rays(Wc, s);
         const WfKernel k = g == 1 ? camera_kernel(wf_camera_kernel(*b, mode, A.eye_on_split != 0))
                                   : trace_kernel(TraceKernels{}, wf_closest_kernel(*b, mode, fixed_options(A, Wc)));
         launch(g == 1 ? TK_CAMERA : TK_CLOSEST, k, blocks, lds, s, Wc, g);
+    }
+    // Generation 1 of a ray pass: the caller's rays share no eye (no packet, no camera cull) and promise none of what
+    // the render's own rays do -- an origin may lie anywhere, so the leaf cull records, exact for origins inside the
+    // padded box widened by 1 (queryroute.hpp), do not cover them, nor does the scene's bound that lets a tc::Fixed
+    // kernel drop a range test of its division.  They take what a QR_FAT ray query takes: the generic fat closest
+    // kernel without a leaf cull, the reference's arithmetic for any finite ray (the counting build's closest kernel
+    // has no leaf cull either).  From generation 2 on every origin is a hit point and the build's own kernels run.
+    const WfBuild *first_build() const { return mode == WF_COUNT ? b : wf_query_build(A.variant, false); }
+    void first_rays(const WfArgs &Wc, hipStream_t s) {
+        const WfBuild *q = first_build();
+        launch(TK_CLOSEST, trace_kernel(TraceKernels{}, mode == WF_COUNT ? wf_closest_kernel(*q, mode, false)
+                                                                         : wf_query_kernel(*q, false)),
+               wf_trace_blocks(q->id, num_cus), wf_ring_bytes(q->ring), s, Wc, 1);
     }
     // shadow trace of generation g (Ws: with the queue's order; dead: the queue may hold dead entries), then
     // wf_resolve of that generation
@@ -1710,13 +1782,17 @@ struct ChunkLauncher {
     // whole chunk in wf_tail(1).  true: wf_shade(1) is next
     bool start(ChunkRun &r) {
         WfArgs &W = r.W;
-        const WfStart s = wf_chunk_start(W, b->packet, A.eye_on_split != 0);
+        const WfStart s = wf_chunk_start(W, b->packet && !rays, A.eye_on_split != 0);
         W.cam_fused = s.cam_fused ? 1 : 0;
-        if (s.camera) hipLaunchKernelGGL(A.list ? wf_camera_list : wf_camera, dim3(sgrid), dim3(256), 0, r.st, A, W);
-        if (s.tail_only) tail(1, r.st, W);
+        if (rays && rays->gather) hipLaunchKernelGGL(wf_camera_rays<true>, dim3(sgrid), dim3(256), 0, r.st, A, W, *rays);
+        else if (rays) hipLaunchKernelGGL(wf_camera_rays<false>, dim3(sgrid), dim3(256), 0, r.st, A, W, *rays);
+        else if (s.camera) hipLaunchKernelGGL(A.list ? wf_camera_list : wf_camera, dim3(sgrid), dim3(256), 0, r.st, A, W);
+        // (a ray pass never hands generation 1 to the tail, whose traversal has the build's leaf cull: first_rays)
+        const bool tail_only = s.tail_only && !rays;
+        if (tail_only) tail(1, r.st, W);
         else closest(W, 1, r.st, nullptr, W.gstack); // camera rays: path order is already coherent
         r.g = 1, r.nin = W.P; // generation 1: one ray per path
-        return !s.tail_only && !err;
+        return !tail_only && !err;
     }
     // wf_shade(g) at its append chunk (wf_app_chunk), then the two queue lengths to r.cnt, async
     void shade(ChunkRun &r) {
@@ -1760,9 +1836,18 @@ struct ChunkLauncher {
     }
 };
 
+int launch_ray_list(uint32_t *list, uint32_t count, uint32_t n_items, hipStream_t st) {
+    if (n_items) hipLaunchKernelGGL(ray_list_kernel, dim3((n_items + 255) / 256), dim3(256), 0, st, list, count, n_items);
+    return (int)hipGetLastError();
+}
+
 int launch_wavefront_chunk(const RenderArgs &A, const WfArgs &W0, int num_cus, hipStream_t st, const WfStreams &ss,
-                           TraceEvents *te) {
-    ChunkLauncher L(A, num_cus, te, WF_DRIVER_CHUNK);
+                           TraceEvents *te, const RaySrc *rays) {
+    ChunkLauncher L(A, num_cus, te, WF_DRIVER_CHUNK, rays);
+    // (a ray pass is a list pass: its generation-0 kernel writes every path's control words)
+    if (rays && (!A.list || W0.cam_fused || W0.cam_lean || W0.ctl_ray || A.cull || L.mode == WF_PERF || !L.b ||
+                 !L.first_build() || W0.gstride < WF_TRACE_BLOCK * wf_trace_blocks(L.first_build()->id, num_cus)))
+        return (int)hipErrorInvalidValue;
     if (int e = L.check(W0)) return e;
     uint32_t cnt[2] = {0u, 0u};
     ChunkRun r = {W0, st, ss.side, ss.fork, ss.join, cnt};

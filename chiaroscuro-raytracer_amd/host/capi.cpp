@@ -368,6 +368,26 @@ int chiaro_raytracer_reset_temporal(chiaro_raytracer *r) {
         },
         CR_E_HIP);
 }
+int chiaro_raytracer_radiance(chiaro_raytracer *r, const float *orig, const float *dir, uint32_t n, uint32_t layers,
+                              float *out) {
+    if (!r || layers < 1 || (n && (!orig || !dir || !out))) return CR_E_INVALID;
+    return guard(
+        [&]() -> int {
+            r->r->radiance(orig, dir, n, layers, out);
+            return CR_OK;
+        },
+        CR_E_HIP);
+}
+int chiaro_raytracer_gather(chiaro_raytracer *r, const float *pos, const float *nrm, uint32_t n, uint32_t layers,
+                            float *out) {
+    if (!r || layers < 1 || (n && (!pos || !nrm || !out))) return CR_E_INVALID;
+    return guard(
+        [&]() -> int {
+            r->r->gather(pos, nrm, n, layers, out);
+            return CR_OK;
+        },
+        CR_E_HIP);
+}
 int chiaro_raytracer_count_map(const chiaro_raytracer *r, uint32_t *counts_out) {
     if (!r || !counts_out || r->r->countMap().empty()) return CR_E_INVALID;
     std::memcpy(counts_out, r->r->countMap().data(), r->r->countMap().size() * sizeof(uint32_t));

@@ -332,6 +332,34 @@ uint32_t RayTracer::rayTraceTemporal(vec3 eye, vec3 center, vec3 up, float yview
     return least;
 }
 
+// radiance() and gather(): cr_radiance / cr_gather of layers 1 .. layers with the Scene's sampling
+static cr_radiance_params radiance_params(const Scene &scene) {
+    cr_radiance_params p{};
+    p.spp = scene.samples;
+    p.k = scene.k;
+    p.background[0] = scene.background.x;
+    p.background[1] = scene.background.y;
+    p.background[2] = scene.background.z;
+    p.seed = scene.seed;
+    p.layer = 1;
+    p.id0 = 0;
+    return p;
+}
+void RayTracer::radiance(const float *orig, const float *dir, uint32_t n, unsigned layers, float *out) {
+    if (group_) throw std::runtime_error("chiaro: radiance runs on one GPU (gpus 1)");
+    const cr_radiance_params p = radiance_params(scene);
+    if (cr_radiance(ctx_, n, orig, dir, &p, layers, out, nullptr) != CR_OK)
+        throw std::runtime_error(std::string("chiaro: radiance failed: ") + cr_last_error(ctx_));
+    cr_get_counters(ctx_, &counters_);
+}
+void RayTracer::gather(const float *pos, const float *nrm, uint32_t n, unsigned layers, float *out) {
+    if (group_) throw std::runtime_error("chiaro: gather runs on one GPU (gpus 1)");
+    const cr_radiance_params p = radiance_params(scene);
+    if (cr_gather(ctx_, n, pos, nrm, &p, layers, out, nullptr) != CR_OK)
+        throw std::runtime_error(std::string("chiaro: gather failed: ") + cr_last_error(ctx_));
+    cr_get_counters(ctx_, &counters_);
+}
+
 void RayTracer::resetTemporal() {
     if (group_) return; // (no history with gpus > 1)
     if (cr_temporal_reset(ctx_) != CR_OK)

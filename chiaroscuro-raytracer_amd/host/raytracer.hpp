@@ -77,6 +77,14 @@ class RayTracer {
                               unsigned layers = 1, unsigned denoiseLevels = 0);
     void resetTemporal(); // the next rayTraceTemporal starts a new history (and the seed again at scene.seed)
     const std::vector<uint32_t> &countMap() const { return countMap_; } // [yres][xres]; empty before rayTraceTemporal
+    /* This build: radiance queries (cr_radiance / cr_gather, include/chiaro_hip.h "radiance queries"): the light the
+     * integrator finds along n caller rays (orig, dir: [n][3], dir not normalised), or the mean incoming radiance under
+     * the cosine density at n surface points (pos, nrm: [n][3]; irradiance is pi times it, and offsetting pos off the
+     * surface is the caller's job).  Layers 1 .. layers of scene.samples samples each, scene.k, scene.background and
+     * scene.seed; ray i draws from the stream of pixel index i.  out [n][3].  The frame, the progressive state and the
+     * temporal history are untouched.  One GPU only. */
+    void radiance(const float *orig, const float *dir, uint32_t n, unsigned layers, float *out);
+    void gather(const float *pos, const float *nrm, uint32_t n, unsigned layers, float *out);
     /* The statistic of the last rayTraceUntil's last check, and the error map [yres][xres] of its frame. */
     const cr_noise_stats &lastNoise() const { return noise_; }
     std::vector<float> noiseMap();

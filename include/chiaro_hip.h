@@ -54,6 +54,10 @@
  *   cr_intersect_device / cr_intersect_shadow_device
  *                        the same two queries on device arrays, on a caller-supplied HIP
  *                        stream, through the render's trace kernels.
+ *   cr_radiance_device / cr_gather_device / cr_radiance / cr_gather
+ *                        RayTracer::sendRay (src/rayTracer.cpp:76-135) along caller rays, or along directions drawn
+ *                        about caller normals, with a frame pixel's sample loop and blend (:59-64) per ray (no
+ *                        reference counterpart as an entry: its only caller of sendRay is the camera loop, :58-62).
  *
  * Threading: one cr_ctx per GPU, not thread-safe; calls on one ctx are serialised.
  */
@@ -603,6 +607,68 @@ int cr_intersect_device(cr_ctx *ctx, uint32_t n, const float *d_orig, const floa
 int cr_intersect_shadow_device(cr_ctx *ctx, uint32_t n, const float *d_orig, const float *d_dir,
                                const float *d_dist, const uint32_t *d_light_tri, uint32_t *d_occluded,
                                void *stream);
+
+/* ---- radiance queries: path-traced light along caller rays ----
+ * "How much light arrives here, from there" for points that are no pixel of a pinhole camera: lightmap and vertex
+ * baking, irradiance and reflection probes.  The integrator is the render's own (RayTracer::sendRay,
+ * src/rayTracer.cpp:76-135), entered with the caller's rays instead of the camera's, and every value is bit for bit
+ * what the reference computes for a camera whose ray is that ray.
+ *
+ * STREAM.  Ray i of a call has stream id j = p->id0 + i.  Sample s of layer L draws from the render's RNG stream
+ * (seed, L, j, s), keyed exactly as pixel index j is.  Its counter starts at 2: draws 0 and 1 are the aim draws.
+ * A batch split over several calls with consecutive id0 therefore gives the bits of one call.
+ *
+ * RAY MODE (cr_radiance_device / cr_radiance).  The aim draws are skipped.  The sample's value is
+ * sendRay(orig_i, dir_i, k = 1) exactly as the render evaluates it from its first closest query on: same draws, same
+ * order, the background on a miss.  dir is used as given, not normalised, as camera rays are.  (The reference makes a
+ * camera ray as d + 0 * ..., which turns a direction component of -0 into +0: a caller who compares against it adds
+ * 0.0f to the directions.)
+ *
+ * GATHER MODE (cr_gather_device / cr_gather).  sx = uniform(-1, 1) from draw 0 and sy = uniform(-1, 1) from draw 1
+ * (the integrator's own uniform), wi = Diffuse::sample_wi(nrm_i, sx, sy) (src/brdf.cpp:57-62, 72-79: the
+ * cosine-weighted direction about the normal), and the value is sendRay(pos_i, wi, 1), continuing at counter 2.  The
+ * pdf is not used: the call returns the MEAN INCOMING RADIANCE under the cosine density.  Irradiance is pi times that
+ * mean; the multiplication is the caller's.  pos is used as given: offsetting it off the surface (the integrator
+ * itself uses 0.001 * normal) is the caller's job.  (Against the same reference a normal component of -0 can show as
+ * a direction component of -0: such a caller adds 0.0f to the normals too.)
+ *
+ * OUTPUT.  d_out [n][3], and d_m2 [n][3] when given, with the arithmetic of a frame pixel: the layer mean is (the
+ * samples summed in sample order) * (1 / spp), out = (old * (L - 1) + mean) / L (layer 1 ignores the old value), and
+ * d_m2 is blended as cr_render_layers_noise_device blends the moment frame.  (d_out, d_m2) is therefore a valid
+ * n x 1 frame for cr_noise_device and cr_noise_select_device.  The _device forms render layers p->layer ..
+ * p->layer + nlayers - 1; for p->layer > 1 the caller guarantees that d_out (and d_m2) hold layer p->layer - 1.
+ * The host forms take host arrays; out and m2 are read (for p->layer > 1) and written.
+ *
+ * The calls run on `stream` and return when complete.  They use the render's work buffers (the rules of
+ * cr_render_layers_list_device, not of the asynchronous query buffers), and leave the ctx's accumulator, moment
+ * accumulator, adaptive state and temporal history untouched.  What does not fit one pass runs as several
+ * (csrc/adaptive.hpp: batches of rays, groups of layers); counters, cr_last_kernel_ms and the trace stats sum over
+ * them.  The first rays run on the general closest trace (cr_trace_stats kind [1]) -- no packet, no camera cull, and,
+ * because an origin may lie anywhere, the fat kernel without the leaf cull, as a ray query outside the scene box
+ * does -- and always as a launch of their own, never inside the tail kernel; every later generation starts at a hit
+ * and runs as the render's does.  "perf_counters" 1 is refused (CR_E_INVALID).
+ * n == 0: CR_OK, nothing launched.
+ * Errors (arguments first, then the device, then the scene): CR_E_INVALID for a null pointer (d_m2 may be null),
+ * spp == 0, k outside 1..64, layer == 0, nlayers == 0, or id0 + n above 0xffffffff.
+ * Non-finite inputs and zero normals are the caller's error: unspecified values for that ray. */
+typedef struct cr_radiance_params {
+    uint32_t spp;        /* samples per layer */
+    int32_t k;           /* max path depth, 1..64 */
+    float background[3]; /* the value of a ray that leaves the scene */
+    uint32_t seed;       /* RNG stream key, the render's */
+    uint32_t layer;      /* first layer, >= 1 */
+    uint32_t id0;        /* stream id of ray 0 */
+} cr_radiance_params;
+/* sizeof the structure as this library was built */
+void cr_radiance_struct_sizes(uint32_t *params_bytes);
+int cr_radiance_device(cr_ctx *ctx, uint32_t n, const float *d_orig, const float *d_dir, const cr_radiance_params *p,
+                       uint32_t nlayers, float *d_out, float *d_m2 /* may be null */, void *stream);
+int cr_gather_device(cr_ctx *ctx, uint32_t n, const float *d_pos, const float *d_nrm, const cr_radiance_params *p,
+                     uint32_t nlayers, float *d_out, float *d_m2 /* may be null */, void *stream);
+int cr_radiance(cr_ctx *ctx, uint32_t n, const float *orig, const float *dir, const cr_radiance_params *p,
+                uint32_t nlayers, float *out, float *m2 /* may be null */);
+int cr_gather(cr_ctx *ctx, uint32_t n, const float *pos, const float *nrm, const cr_radiance_params *p,
+              uint32_t nlayers, float *out, float *m2 /* may be null */);
 
 int cr_get_counters(cr_ctx *ctx, cr_counters *out);
 /* Device time (ms) of the last render kernel, HIP events on its own stream. */

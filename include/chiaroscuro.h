@@ -15,6 +15,9 @@
  *                            an edge-avoiding filter over such a frame (this build; cr_denoise)
  *   chiaro_raytracer_raytrace_temporal / _reset_temporal / _count_map, chiaro_preview_set_temporal
  *                            a frame's history carried to a moved camera (this build; cr_render_temporal)
+ *   chiaro_raytracer_radiance / _gather
+ *                            RayTracer::sendRay (src/rayTracer.cpp:76-135) along caller rays (this build; cr_radiance,
+ *                            cr_gather)
  *   chiaro_raytracer_raytrace_until / _noise / _noise_map
  *                            rayTrace repeated until a noise target is met (this build; the accumulation of
  *                            src/rayTracer.cpp:18-33,59-64 with a second-moment frame, cr_render_until)
@@ -139,6 +142,16 @@ int chiaro_raytracer_raytrace_temporal(chiaro_raytracer *r, const float eye[3], 
                                        uint32_t *min_count_out);
 int chiaro_raytracer_reset_temporal(chiaro_raytracer *r);
 int chiaro_raytracer_count_map(const chiaro_raytracer *r, uint32_t *counts_out);
+/* RayTracer::radiance / RayTracer::gather (cr_radiance / cr_gather, include/chiaro_hip.h "radiance queries"): the
+ * path-traced light along n caller rays (orig, dir: [n][3], dir not normalised), or the mean incoming radiance under
+ * the cosine density at n surface points (pos, nrm: [n][3]; irradiance is pi times it; offsetting pos off the surface
+ * is the caller's job).  Layers 1 .. layers with the Scene's samples, k, background and seed; ray i draws from the
+ * stream of pixel index i.  out [n][3].  The frame, the progressive state and the temporal history are untouched.
+ * CR_E_INVALID for a null pointer or layers == 0; CR_E_HIP with chiaro_last_error otherwise.  One GPU only. */
+int chiaro_raytracer_radiance(chiaro_raytracer *r, const float *orig, const float *dir, uint32_t n, uint32_t layers,
+                              float *out);
+int chiaro_raytracer_gather(chiaro_raytracer *r, const float *pos, const float *nrm, uint32_t n, uint32_t layers,
+                            float *out);
 const float *chiaro_raytracer_pixels(const chiaro_raytracer *r);
 const uint8_t *chiaro_raytracer_data(chiaro_raytracer *r);
 float chiaro_raytracer_maxval(const chiaro_raytracer *r);
