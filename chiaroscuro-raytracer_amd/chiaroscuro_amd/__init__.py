@@ -234,6 +234,53 @@ def radiance_params(spp, k, seed, background=(0.0, 0.0, 0.0), layer=1, id0=0) ->
                             int(layer), int(id0))
 
 
+class CrBakeParams(C.Structure):
+    """cr_bake_params (include/chiaro_hip.h "lightmap baking")."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("spp", C.c_uint32), ("k", C.c_int32),
+                ("background", C.c_float * 3), ("seed", C.c_uint32), ("offset", C.c_float)]
+
+
+class CrBakeStats(C.Structure):
+    """cr_bake_stats of a cr_bake."""
+    _fields_ = [("covered", C.c_uint64), ("texel_layers", C.c_uint64), ("active", C.c_uint64),
+                ("layers", C.c_uint32), ("checks", C.c_uint32), ("max_err", C.c_float), ("reserved", C.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {"covered": int(self.covered), "texel_layers": int(self.texel_layers), "active": int(self.active),
+                "layers": int(self.layers), "checks": int(self.checks), "max_err": float(self.max_err)}
+
+
+def bake_params(width, height, spp=None, k=None, seed=None, background=None, offset=None) -> CrBakeParams:
+    """cr_bake_params_default (spp 1, k 6, black, seed 0, offset 0.001) at width x height with the given fields
+    replaced."""
+    bp = CrBakeParams()
+    libs()[0].cr_bake_params_default(C.byref(bp))
+    bp.width, bp.height = int(width), int(height)
+    if spp is not None:
+        bp.spp = int(spp)
+    if k is not None:
+        bp.k = int(k)
+    if seed is not None:
+        bp.seed = int(seed) & 0xffffffff
+    if background is not None:
+        bp.background = (C.c_float * 3)(*[float(v) for v in background])
+    if offset is not None:
+        bp.offset = float(offset)
+    return bp
+
+
+def bake_atlas_grid(n_tris: int, cell: int, gutter: float = 0.25):
+    """cr_bake_atlas_grid: (W, H, uv [n_tris][6] float32) of the grid atlas -- triangle t in cell (t % cols, t / cols)
+    of a ceil(sqrt(n_tris))-column grid of cell x cell texels.  Needs no device."""
+    w, h = C.c_uint32(0), C.c_uint32(0)
+    uv = np.zeros((max(int(n_tris), 0), 6), np.float32)
+    rc = libs()[0].cr_bake_atlas_grid(int(n_tris), int(cell), float(gutter), C.byref(w), C.byref(h),
+                                      _ptr(uv) if uv.size else None)
+    if rc:
+        raise RuntimeError("cr_bake_atlas_grid: %s" % CR_ERRORS.get(rc, rc))
+    return int(w.value), int(h.value), uv
+
+
 def temporal_params(depth_tol=None, normal_min=None, max_history=None) -> CrTemporalParams:
     """cr_temporal_params_default (0.05, 0.9, 65536) with the given fields replaced."""
     tp = CrTemporalParams()
@@ -275,7 +322,9 @@ HIP_SYMBOLS = ("cr_create", "cr_destroy", "cr_last_error", "cr_upload_scene", "c
                "cr_denoise_device", "cr_denoise",
                "cr_temporal_params_default", "cr_temporal_struct_sizes", "cr_reproject_device", "cr_render_temporal",
                "cr_temporal_reset", "cr_temporal_history",
-               "cr_radiance_struct_sizes", "cr_radiance_device", "cr_gather_device", "cr_radiance", "cr_gather")
+               "cr_radiance_struct_sizes", "cr_radiance_device", "cr_gather_device", "cr_radiance", "cr_gather",
+               "cr_radiance_list_device", "cr_gather_list_device", "cr_bake_params_default", "cr_bake_struct_sizes",
+               "cr_bake_surface_device", "cr_bake_dilate_device", "cr_bake_atlas_grid", "cr_bake")
 HOST_SYMBOLS = ("chiaro_last_error", "chiaro_scene_create", "chiaro_scene_info_get", "chiaro_scene_destroy",
                 "chiaro_model_create", "chiaro_model_load", "chiaro_model_num_meshes", "chiaro_model_num_triangles",
                 "chiaro_model_num_textures", "chiaro_model_triangles", "chiaro_model_texture",
@@ -296,7 +345,7 @@ HOST_SYMBOLS = ("chiaro_last_error", "chiaro_scene_create", "chiaro_scene_info_g
                 "chiaro_raytracer_adaptive", "chiaro_raytracer_layer_map", "chiaro_raytracer_denoise",
                 "chiaro_raytracer_denoised", "chiaro_raytracer_raytrace_temporal", "chiaro_raytracer_reset_temporal",
                 "chiaro_raytracer_count_map", "chiaro_preview_set_temporal", "chiaro_raytracer_radiance",
-                "chiaro_raytracer_gather")
+                "chiaro_raytracer_gather", "chiaro_raytracer_bake", "chiaro_raytracer_bake_adaptive")
 
 P = C.c_void_p
 FP = C.POINTER(C.c_float)
@@ -438,6 +487,16 @@ def libs():
         _sig(hip, name, C.c_int, [CTX, C.c_uint32, P, P, RP, C.c_uint32, P, P, P])
     for name in ("cr_radiance", "cr_gather"):
         _sig(hip, name, C.c_int, [CTX, C.c_uint32, FP, FP, RP, C.c_uint32, FP, FP])
+    for name in ("cr_radiance_list_device", "cr_gather_list_device"):
+        _sig(hip, name, C.c_int, [CTX, C.c_uint32, P, P, P, C.c_uint32, RP, C.c_uint32, P, P, P])
+    BP = C.POINTER(CrBakeParams)
+    _sig(hip, "cr_bake_params_default", None, [BP])
+    _sig(hip, "cr_bake_struct_sizes", None, [UP, UP])
+    _sig(hip, "cr_bake_surface_device", C.c_int, [CTX, BP, P, P, P, P, P, P, P])
+    _sig(hip, "cr_bake_dilate_device", C.c_int, [CTX, C.c_uint32, C.c_uint32, P, C.c_uint32, P, P, P])
+    _sig(hip, "cr_bake_atlas_grid", C.c_int, [C.c_uint32, C.c_uint32, C.c_float, UP, UP, FP])
+    _sig(hip, "cr_bake", C.c_int, [CTX, BP, FP, C.c_uint32, C.POINTER(CrAdaptiveParams), C.POINTER(CrNoiseParams),
+                                   C.c_uint32, FP, FP, UP, UP, FP, C.POINTER(CrBakeStats)])
 
     _sig(host, "chiaro_last_error", C.c_char_p, [])
     _sig(host, "chiaro_scene_create", P, [C.c_int, C.POINTER(C.c_char_p)])
@@ -479,6 +538,9 @@ def libs():
     _sig(host, "chiaro_preview_set_temporal", C.c_int, [P, C.c_int])
     _sig(host, "chiaro_raytracer_radiance", C.c_int, [P, FP, FP, C.c_uint32, C.c_uint32, FP])
     _sig(host, "chiaro_raytracer_gather", C.c_int, [P, FP, FP, C.c_uint32, C.c_uint32, FP])
+    _sig(host, "chiaro_raytracer_bake", C.c_int, [P, C.c_uint32, C.c_uint32, FP, C.c_uint32, C.c_uint32, FP, FP])
+    _sig(host, "chiaro_raytracer_bake_adaptive", C.c_int, [P, C.c_uint32, C.c_uint32, FP, C.c_float, C.c_uint32,
+                                                           C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, FP, FP, UP])
     _sig(host, "chiaro_raytracer_pixels", FP, [P])
     _sig(host, "chiaro_raytracer_data", C.POINTER(C.c_uint8), [P])
     _sig(host, "chiaro_raytracer_maxval", C.c_float, [P])
@@ -988,6 +1050,70 @@ class Device:
         """cr_gather on host arrays (see gather_device)."""
         return self._radiance_host(libs()[0].cr_gather, "cr_gather", pos, nrm, rp, nlayers, out, m2)
 
+    def radiance_list_device(self, n: int, d_orig_ptr: int, d_dir_ptr: int, d_list_ptr: int, n_list: int,
+                             rp: CrRadianceParams, nlayers: int, d_out_ptr: int, d_m2_ptr: int = 0, stream: int = 0):
+        """cr_radiance_list_device: radiance_device for the n_list listed entries (uint32 indices; 0xffffffff or an
+        index >= n: skipped) of the n-entry device arrays alone; no other entry is read or written."""
+        self._chk(libs()[0].cr_radiance_list_device(self._c, int(n), C.c_void_p(d_orig_ptr or None),
+                                                    C.c_void_p(d_dir_ptr or None), C.c_void_p(d_list_ptr or None),
+                                                    int(n_list), C.byref(rp), int(nlayers),
+                                                    C.c_void_p(d_out_ptr or None), C.c_void_p(d_m2_ptr or None),
+                                                    C.c_void_p(stream)), "cr_radiance_list_device")
+
+    def gather_list_device(self, n: int, d_pos_ptr: int, d_nrm_ptr: int, d_list_ptr: int, n_list: int,
+                           rp: CrRadianceParams, nlayers: int, d_out_ptr: int, d_m2_ptr: int = 0, stream: int = 0):
+        """cr_gather_list_device: gather_device for the listed entries alone (see radiance_list_device)."""
+        self._chk(libs()[0].cr_gather_list_device(self._c, int(n), C.c_void_p(d_pos_ptr or None),
+                                                  C.c_void_p(d_nrm_ptr or None), C.c_void_p(d_list_ptr or None),
+                                                  int(n_list), C.byref(rp), int(nlayers),
+                                                  C.c_void_p(d_out_ptr or None), C.c_void_p(d_m2_ptr or None),
+                                                  C.c_void_p(stream)), "cr_gather_list_device")
+
+    def bake_surface_device(self, bp: CrBakeParams, d_uv_ptr: int, d_owner_ptr: int, d_pos_ptr: int, d_nrm_ptr: int,
+                            d_list_ptr: int, d_count_ptr: int, stream: int = 0):
+        """cr_bake_surface_device: for the bp.width x bp.height lightmap over the UVs d_uv ([n_tris][6] float, 0: the
+        scene's own) the owner map (uint32 [H][W], 0xffffffff: none), the surface point and normal under each texel
+        centre ([H][W][3], zeros where unowned), the owned texel indices ascending (room W * H) and their count (one
+        device word).  Enqueued on `stream`."""
+        self._chk(libs()[0].cr_bake_surface_device(self._c, C.byref(bp), C.c_void_p(d_uv_ptr or None),
+                                                   C.c_void_p(d_owner_ptr or None), C.c_void_p(d_pos_ptr or None),
+                                                   C.c_void_p(d_nrm_ptr or None), C.c_void_p(d_list_ptr or None),
+                                                   C.c_void_p(d_count_ptr or None), C.c_void_p(stream)),
+                  "cr_bake_surface_device")
+
+    def bake_dilate_device(self, width: int, height: int, d_owner_ptr: int, passes: int, d_in_ptr: int, d_out_ptr: int,
+                           stream: int = 0):
+        """cr_bake_dilate_device: `passes` dilation passes of the device map d_in [H][W][3] into d_out (no alias): an
+        unfilled texel with filled 8-neighbours becomes their mean.  Enqueued on `stream`."""
+        self._chk(libs()[0].cr_bake_dilate_device(self._c, int(width), int(height), C.c_void_p(d_owner_ptr or None),
+                                                  int(passes), C.c_void_p(d_in_ptr or None),
+                                                  C.c_void_p(d_out_ptr or None), C.c_void_p(stream)),
+                  "cr_bake_dilate_device")
+
+    def bake(self, bp: CrBakeParams, uv=None, nlayers: int = 1, adaptive: CrAdaptiveParams | None = None,
+             threshold: float = 0.0, floor: float = 1e-3, dilate: int | None = None, want_m2: bool = True) -> dict:
+        """cr_bake: the lightmap of uv ([n_tris][6] float32, None: the scene's own UVs) -- the mean incoming radiance
+        under the cosine density at each covered texel, texel y * W + x on stream y * W + x -- with nlayers layers, or
+        (adaptive given) cr_render_adaptive's loop with the noise check (threshold, floor).  Returns {"lightmap",
+        "m2" (or None) [H][W][3], "layers", "owner" uint32 [H][W], "dilated" ([H][W][3] after `dilate` passes, None
+        when dilate is None), "stats"}."""
+        h, w = int(bp.height), int(bp.width)
+        if uv is not None:
+            uv = np.ascontiguousarray(uv, np.float32)
+            assert uv.size == 6 * self.scene_triangles()
+        out = np.zeros((h, w, 3), np.float32)
+        mom = np.zeros((h, w, 3), np.float32) if want_m2 else None
+        lmap, owner = np.zeros((h, w), np.uint32), np.zeros((h, w), np.uint32)
+        dil = np.zeros((h, w, 3), np.float32) if dilate is not None else None
+        np_ = CrNoiseParams(float(threshold), float(floor))
+        st = CrBakeStats()
+        self._chk(libs()[0].cr_bake(self._c, C.byref(bp), _ptr(uv) if uv is not None else None, int(nlayers),
+                                    C.byref(adaptive) if adaptive is not None else None, C.byref(np_),
+                                    int(dilate or 0), _ptr(out), _ptr(mom) if want_m2 else None,
+                                    _ptr(lmap, C.c_uint32), _ptr(owner, C.c_uint32),
+                                    _ptr(dil) if dil is not None else None, C.byref(st)), "cr_bake")
+        return {"lightmap": out, "m2": mom, "layers": lmap, "owner": owner, "dilated": dil, "stats": st.as_dict()}
+
     def intersect_shadow_device(self, n: int, d_orig_ptr: int, d_dir_ptr: int, d_dist_ptr: int, d_light_ptr: int,
                                 d_occluded_ptr: int, stream: int = 0):
         """cr_intersect_shadow_device: n shadow queries on device arrays, enqueued on `stream`."""
@@ -1297,6 +1423,33 @@ class RayTracer:
         if rc:
             raise RuntimeError("rayTraceTemporal: " + _host_err())
         return int(least.value)
+
+    def bakeLightmap(self, width, height, uv=None, layers=1, dilate=None, threshold=None, maxLayers=None,
+                     floor=1e-3, minLayers=1, checkEvery=1):
+        """The width x height lightmap over the lightmap UVs uv ([triangles][6]; None: the grid atlas of the scene's
+        triangles at the largest cell that fits): the mean incoming radiance under the cosine density at each
+        covered texel, with the Scene's samples, k, background and seed (cr_bake).  `layers` layers, or -- threshold
+        and maxLayers given -- further layers only where the error is above threshold.  Returns the map
+        [height][width][3]; with dilate (passes) given (map, dilated map); the adaptive form appends the layer map."""
+        w, h = int(width), int(height)
+        if uv is not None:
+            uv = np.ascontiguousarray(uv, np.float32)
+        out = np.zeros((h, w, 3), np.float32)
+        dil = np.zeros((h, w, 3), np.float32) if dilate is not None else None
+        puv = _ptr(uv) if uv is not None else None
+        pdil = _ptr(dil) if dil is not None else None
+        res = [out] + ([dil] if dil is not None else [])
+        if threshold is None:
+            rc = libs()[1].chiaro_raytracer_bake(self._h, w, h, puv, int(layers), int(dilate or 0), _ptr(out), pdil)
+        else:
+            lmap = np.zeros((h, w), np.uint32)
+            rc = libs()[1].chiaro_raytracer_bake_adaptive(self._h, w, h, puv, float(threshold), int(maxLayers),
+                                                          float(floor), int(minLayers), int(checkEvery),
+                                                          int(dilate or 0), _ptr(out), pdil, _ptr(lmap, C.c_uint32))
+            res.append(lmap)
+        if rc:
+            raise RuntimeError("bakeLightmap: " + _host_err())
+        return res[0] if len(res) == 1 else tuple(res)
 
     def _radiance(self, fn, name, a, b, layers):
         a = np.ascontiguousarray(a, np.float32).reshape(-1, 3)

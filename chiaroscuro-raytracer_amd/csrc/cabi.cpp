@@ -5,6 +5,7 @@
 // per-launch HIP events.  No C++ exception or hipError_t crosses the ABI.
 #include "ctx.hpp"
 #include "adaptive.hpp"
+#include "bake.hpp"
 #include "denoise.hpp"
 #include "radiance.hpp"
 #include "scenelayout.hpp"
@@ -961,7 +962,7 @@ cr_ctx *cr_create(int device) {
         c->lane_ev[0].create(false) != hipSuccess || c->lane_ev[1].create(false) != hipSuccess ||
         c->hcnt.create(4) != hipSuccess || c->ev0.create(true) != hipSuccess || c->ev1.create(true) != hipSuccess ||
         c->q_ev.create(false) != hipSuccess || c->sel_ev.create(false) != hipSuccess ||
-        c->dn_ev.create(false) != hipSuccess ||
+        c->dn_ev.create(false) != hipSuccess || c->bake_ev.create(false) != hipSuccess ||
         c->d_counters.grow(cr::CTR_SLOTS * sizeof(unsigned long long)) != CR_OK) {
         delete c; // all or nothing: what was created goes now, while its device is current
         return (c = new cr_ctx())->err = "device init failed", c;
@@ -977,6 +978,7 @@ void cr_destroy(cr_ctx *c) {
         if (c->q_pending) hipEventSynchronize(c->q_ev); // a pending query still uses d_query
         if (c->sel_pending) hipEventSynchronize(c->sel_ev); // ... a pending selection d_select
         if (c->dn_pending) hipEventSynchronize(c->dn_ev);   // ... a pending guide or filter call d_guide / d_dn
+        if (c->bake_pending) hipEventSynchronize(c->bake_ev); // ... a pending dilation d_bake_level
     }
     delete c; // (a ctx without a device holds no handle: cr_create)
 }
@@ -1371,6 +1373,254 @@ int cr_render_adaptive(cr_ctx *c, const cr_camera *cam, const cr_render_params *
     if (layers_out) HIPCHK(hipMemcpyAsync(layers_out, map, (size_t)npix * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     *stats_out = out;
+    return CR_OK;
+}
+
+// ---- list forms of the radiance queries, lightmap baking ----
+// Layers p->layer .. + nlayers - 1 of the listed entries of the n rays (a, b) blended into d_out (and d_m2): render_list
+// with a RaySrc -- the n x 1 frame, each of ad_plan's passes over its part of the list padded to whole tiles
+static int run_radiance_list(cr_ctx *c, uint32_t n, const float *d_a, const float *d_b, bool gather,
+                             const cr_radiance_params *p, uint32_t nlayers, const uint32_t *d_list, uint32_t n_list,
+                             float *d_out, float *d_m2, hipStream_t st, PassTotals &sum) {
+    const uint32_t max_nl = c->kernel != 2 || c->wf_lanes != 1 || c->full_counters ? 1u : 32u; // (cr_layers_per_pass's rule)
+    const cr::AdPlanIn in = cr::rad_plan_in(n_list, nlayers, p->spp, max_nl,
+                                            std::min<uint64_t>(c->wf_paths, wf_path_cap(c, p->k)), c->sample_buf);
+    const cr_camera cam{}; // (no kernel of a ray pass reads a camera)
+    const cr::RaySrc src{d_a, d_b, p->id0, gather ? 1 : 0};
+    for (const cr::AdPass &ps : cr::ad_plan(in)) {
+        const uint32_t items = (uint32_t)cr::ad_padded(ps.count, in.tile);
+        if (int r = grow(c, c->d_list_pad, (size_t)items * sizeof(uint32_t))) return r;
+        HIPCHK(hipMemsetAsync(c->d_list_pad.ptr, 0xff, (size_t)items * sizeof(uint32_t), st)); // LIST_SKIP
+        HIPCHK(hipMemcpyAsync(c->d_list_pad.ptr, d_list + ps.first, (size_t)ps.count * sizeof(uint32_t),
+                              hipMemcpyDeviceToDevice, st));
+        cr_render_params t{};
+        t.xres = n, t.yres = 1, t.spp = p->spp, t.k = p->k;
+        std::memcpy(t.background, p->background, sizeof t.background);
+        t.seed = p->seed, t.layer = p->layer + ps.layer0, t.rank = 0, t.nranks = 1, t.tile = in.tile;
+        if (int rc = crx::run_render(c, &cam, &t, d_out, cr::MODE_BLEND, st, ps.nl, 0, 1, 0, d_m2,
+                                     c->d_list_pad.as<uint32_t>(), items, &src))
+            return rc;
+        sum.add(c);
+    }
+    return CR_OK;
+}
+static int radiance_list_device(cr_ctx *c, uint32_t n, const float *d_a, const float *d_b, bool gather,
+                                const uint32_t *d_list, uint32_t n_list, const cr_radiance_params *p, uint32_t nlayers,
+                                float *d_out, float *d_m2, void *stream) {
+    if (!c) return CR_E_INVALID;
+    const char *msg = cr::rad_check(n, d_a && d_b && d_out, p != nullptr, p ? p->spp : 0, p ? p->k : 0, p ? p->layer : 0,
+                                    p ? p->id0 : 0, nlayers);
+    if (!msg) msg = cr::rad_check_list(n, n_list, d_list != nullptr);
+    if (msg) return fail(c, CR_E_INVALID, msg);
+    if (int rc = enter(c)) return rc;
+    if (!c->has_scene) return fail(c, CR_E_NOSCENE, "no scene uploaded");
+    if (n == 0 || n_list == 0) return CR_OK;
+    PassTotals sum;
+    if (int rc = run_radiance_list(c, n, d_a, d_b, gather, p, nlayers, d_list, n_list, d_out, d_m2, (hipStream_t)stream, sum))
+        return rc;
+    sum.store(c);
+    return CR_OK;
+}
+int cr_radiance_list_device(cr_ctx *c, uint32_t n, const float *d_orig, const float *d_dir, const uint32_t *d_list,
+                            uint32_t n_list, const cr_radiance_params *p, uint32_t nlayers, float *d_out, float *d_m2,
+                            void *stream) {
+    return radiance_list_device(c, n, d_orig, d_dir, false, d_list, n_list, p, nlayers, d_out, d_m2, stream);
+}
+int cr_gather_list_device(cr_ctx *c, uint32_t n, const float *d_pos, const float *d_nrm, const uint32_t *d_list,
+                          uint32_t n_list, const cr_radiance_params *p, uint32_t nlayers, float *d_out, float *d_m2,
+                          void *stream) {
+    return radiance_list_device(c, n, d_pos, d_nrm, true, d_list, n_list, p, nlayers, d_out, d_m2, stream);
+}
+
+void cr_bake_params_default(cr_bake_params *out) {
+    if (!out) return;
+    *out = cr_bake_params{};
+    out->spp = 1, out->k = 6, out->offset = 0.001f;
+}
+void cr_bake_struct_sizes(uint32_t *params_bytes, uint32_t *stats_bytes) {
+    if (params_bytes) *params_bytes = (uint32_t)sizeof(cr_bake_params);
+    if (stats_bytes) *stats_bytes = (uint32_t)sizeof(cr_bake_stats);
+}
+int cr_bake_atlas_grid(uint32_t n_tris, uint32_t cell, float gutter, uint32_t *W_out, uint32_t *H_out, float *uv_out) {
+    if (cr::bake_atlas_check(n_tris, cell, gutter)) return CR_E_INVALID;
+    cr::bake_atlas_grid(n_tris, cell, gutter, W_out, H_out, uv_out);
+    return CR_OK;
+}
+// The surface of the W x H map on st; the compaction's scratch is the selection's, under its rule (enqueue_select)
+static int enqueue_bake_surface(cr_ctx *c, uint32_t W, uint32_t H, float offset, const float *d_uv, uint32_t *owner,
+                                float *pos, float *nrm, uint32_t *list, uint32_t *count, hipStream_t st) {
+    HIPCHK(hipSetDevice(c->device));
+    if (int r = grow(c, c->d_select, cr::SELECT_SCRATCH * sizeof(uint32_t))) return r;
+    if (c->sel_pending && st != c->sel_stream) HIPCHK(hipStreamWaitEvent(st, c->sel_ev, 0));
+    cr::BakeArgs B{};
+    B.tri = c->S.tri;
+    B.mat_n = c->S.mat_n;
+    B.uv = d_uv ? d_uv : (const float *)c->S.mat_uv;
+    B.n_tris = c->n_tris;
+    B.W = W, B.H = H;
+    B.offset = offset;
+    B.owner = owner, B.pos = pos, B.nrm = nrm, B.list = list, B.count = count;
+    B.scratch = c->d_select.as<uint32_t>();
+    const int e = cr::launch_bake_surface(B, st);
+    const hipError_t ev = hipEventRecord(c->sel_ev, st);
+    c->sel_pending = ev == hipSuccess;
+    c->sel_stream = st;
+    if (e) return hip_fail(c, (hipError_t)e, "bake surface kernel launch");
+    if (ev != hipSuccess) return hip_fail(c, ev, "hipEventRecord(bake surface)");
+    return CR_OK;
+}
+int cr_bake_surface_device(cr_ctx *c, const cr_bake_params *p, const float *d_uv, uint32_t *d_owner, float *d_pos,
+                           float *d_nrm, uint32_t *d_list, uint32_t *d_count, void *stream) {
+    if (!c) return CR_E_INVALID;
+    if (const char *msg = cr::bake_check_surface(p != nullptr, p ? p->width : 0, p ? p->height : 0, p ? p->offset : 0.f,
+                                                 d_owner && d_pos && d_nrm && d_list && d_count))
+        return fail(c, CR_E_INVALID, msg);
+    if (int rc = enter(c, false)) return rc;
+    if (!c->has_scene) return fail(c, CR_E_NOSCENE, "no scene uploaded");
+    return enqueue_bake_surface(c, p->width, p->height, p->offset, d_uv, d_owner, d_pos, d_nrm, d_list, d_count,
+                                (hipStream_t)stream);
+}
+// `passes` dilation passes of in into out on st; the level map is the ctx's (bake_ev: dn_acquire's rule)
+static int enqueue_bake_dilate(cr_ctx *c, uint32_t W, uint32_t H, const uint32_t *owner, uint32_t passes, const float *in,
+                               float *out, hipStream_t st) {
+    HIPCHK(hipSetDevice(c->device));
+    passes = cr::bake_dilate_passes(W, H, passes);
+    cr::DilateArgs D{};
+    D.W = W, D.H = H, D.owner = owner, D.in = in, D.out = out;
+    if (passes) {
+        DevBuf &b = c->d_bake_level;
+        const size_t need = (size_t)W * H * sizeof(uint32_t);
+        if (c->bake_pending && (!b.ptr || need > b.cap)) {
+            HIPCHK(hipEventSynchronize(c->bake_ev));
+            c->bake_pending = false;
+        } else if (c->bake_pending && st != c->bake_stream) {
+            HIPCHK(hipStreamWaitEvent(st, c->bake_ev, 0));
+        }
+        if (int r = grow(c, b, need, "dilation level map")) return r;
+        D.level = b.as<uint32_t>();
+    }
+    const int e = cr::launch_bake_dilate(D, passes, st);
+    if (passes) {
+        const hipError_t ev = hipEventRecord(c->bake_ev, st);
+        c->bake_pending = ev == hipSuccess;
+        c->bake_stream = st;
+        if (!e && ev != hipSuccess) return hip_fail(c, ev, "hipEventRecord(dilation)");
+    }
+    if (e) return hip_fail(c, (hipError_t)e, "dilation kernel launch");
+    return CR_OK;
+}
+int cr_bake_dilate_device(cr_ctx *c, uint32_t W, uint32_t H, const uint32_t *d_owner, uint32_t passes, const float *d_in,
+                          float *d_out, void *stream) {
+    if (!c) return CR_E_INVALID;
+    if (const char *msg = cr::bake_check_dilate(W, H, d_owner && d_in && d_out, d_in == d_out))
+        return fail(c, CR_E_INVALID, msg);
+    if (int rc = enter(c, false)) return rc;
+    return enqueue_bake_dilate(c, W, H, d_owner, passes, d_in, d_out, (hipStream_t)stream);
+}
+
+int cr_bake(cr_ctx *c, const cr_bake_params *p, const float *uv, uint32_t nlayers, const cr_adaptive_params *ap,
+            const cr_noise_params *np, uint32_t dilate, float *lightmap_out, float *m2_out, uint32_t *layers_out,
+            uint32_t *owner_out, float *dilated_out, cr_bake_stats *stats_out) {
+    if (!c) return CR_E_INVALID;
+    if (const char *msg = cr::bake_check_surface(p != nullptr, p ? p->width : 0, p ? p->height : 0, p ? p->offset : 0.f,
+                                                 lightmap_out != nullptr))
+        return fail(c, CR_E_INVALID, p && !lightmap_out ? "null lightmap output" : msg);
+    if (ap) {
+        if (int r = check_noise_params(c, np)) return r;
+        if (ap->check_every < 1 || ap->max_layers < 1 || ap->min_layers > ap->max_layers)
+            return fail(c, CR_E_INVALID, "cr_bake: check_every >= 1 and min_layers <= max_layers, max_layers >= 1");
+    }
+    if (const char *msg = cr::bake_check_sampling(p->spp, p->k, ap ? ap->max_layers : nlayers))
+        return fail(c, CR_E_INVALID, msg);
+    if (int rc = enter(c)) return rc;
+    if (!c->has_scene) return fail(c, CR_E_NOSCENE, "no scene uploaded");
+    const uint32_t W = p->width, H = p->height, npix = W * H;
+    const size_t n = (size_t)npix;
+    // one grow-only buffer, 256-B aligned parts
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        const size_t at = off;
+        off += (bytes + 255) & ~(size_t)255;
+        return at;
+    };
+    const size_t o_owner = take(n * 4), o_pos = take(n * 12), o_nrm = take(n * 12), o_list = take(n * 4), o_count = take(4),
+                 o_frame = take(n * 12), o_m2 = take(n * 12), o_map = take(n * 4),
+                 o_act0 = take(ap ? n * 4 : 0), o_act1 = take(ap ? n * 4 : 0),
+                 o_uv = take(uv ? (size_t)c->n_tris * 24 : 0), o_dil = take(dilated_out ? n * 12 : 0);
+    if (int r = grow(c, c->d_bake, off, "bake buffers")) return r;
+    char *base = (char *)c->d_bake.ptr;
+    uint32_t *owner = (uint32_t *)(base + o_owner), *list0 = (uint32_t *)(base + o_list);
+    uint32_t *d_count = (uint32_t *)(base + o_count), *map = (uint32_t *)(base + o_map);
+    uint32_t *act[2] = {(uint32_t *)(base + o_act0), (uint32_t *)(base + o_act1)};
+    float *pos = (float *)(base + o_pos), *nrm = (float *)(base + o_nrm), *frame = (float *)(base + o_frame);
+    float *m2 = (float *)(base + o_m2), *d_uv = uv ? (float *)(base + o_uv) : nullptr;
+    hipStream_t st = c->stream;
+    if (uv) HIPCHK(hipMemcpyAsync(d_uv, uv, (size_t)c->n_tris * 24, hipMemcpyHostToDevice, st));
+    if (int rc = enqueue_bake_surface(c, W, H, p->offset, d_uv, owner, pos, nrm, list0, d_count, st)) return rc;
+    HIPCHK(hipMemsetAsync(frame, 0, n * 12, st));
+    HIPCHK(hipMemsetAsync(m2, 0, n * 12, st));
+    HIPCHK(hipMemsetAsync(map, 0, n * 4, st));
+    uint32_t covered = 0;
+    HIPCHK(hipMemcpyAsync(&covered, d_count, sizeof covered, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    cr_radiance_params rp{};
+    rp.spp = p->spp, rp.k = p->k, rp.seed = p->seed, rp.layer = 1, rp.id0 = 0; // (texel t is stream t)
+    std::memcpy(rp.background, p->background, sizeof rp.background);
+    cr_bake_stats out{};
+    out.covered = covered;
+    PassTotals sum;
+    int rc = CR_OK;
+    if (!ap && covered) {
+        if ((rc = run_radiance_list(c, npix, pos, nrm, true, &rp, nlayers, list0, covered, frame, m2, st, sum))) return rc;
+        if (int e = cr::launch_list_fill(map, list0, covered, npix, nlayers, st))
+            return hip_fail(c, (hipError_t)e, "layer map kernel launch");
+        out.layers = nlayers;
+        out.texel_layers = (uint64_t)covered * nlayers;
+    } else if (covered) {
+        // cr_render_adaptive's loop: the covered list is the first active set
+        if (int r = grow(c, c->d_sstats, sizeof(cr_select_stats))) return r;
+        const uint32_t *list = list0;
+        uint32_t n_list = covered, cur = 0;
+        uint64_t active = covered;
+        for (uint32_t L = 0; L < ap->max_layers && active;) {
+            const cr::AdStep s = cr::ad_step(L, ap->min_layers, ap->max_layers, ap->check_every);
+            rp.layer = L + 1;
+            if ((rc = run_radiance_list(c, npix, pos, nrm, true, &rp, s.n, list, n_list, frame, m2, st, sum))) return rc;
+            L += s.n;
+            out.layers = L;
+            out.texel_layers += active * s.n;
+            if (int e = cr::launch_list_fill(map, list, n_list, npix, L, st))
+                return hip_fail(c, (hipError_t)e, "layer map kernel launch");
+            if (!s.check) continue;
+            uint32_t *sel = act[cur ^ 1];
+            cr_select_stats ss{};
+            if ((rc = enqueue_select(c, npix, 1, L, p->spp, np, frame, m2, list, n_list, sel,
+                                     c->d_sstats.as<cr_select_stats>(), st)))
+                return rc;
+            HIPCHK(hipMemcpyAsync(&ss, c->d_sstats.ptr, sizeof(ss), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            out.checks++;
+            out.active = ss.above;
+            out.max_err = ss.max_err;
+            if (L == ap->max_layers) break; // (the check served the statistic only)
+            if (ss.above < active) { // texels dropped: the selected ones are the new active set
+                list = sel, n_list = (uint32_t)ss.above, cur ^= 1;
+                active = ss.above;
+            }
+        }
+    }
+    sum.store(c);
+    if (dilated_out) {
+        float *dil = (float *)(base + o_dil);
+        if ((rc = enqueue_bake_dilate(c, W, H, owner, dilate, frame, dil, st))) return rc;
+        HIPCHK(hipMemcpyAsync(dilated_out, dil, n * 12, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipMemcpyAsync(lightmap_out, frame, n * 12, hipMemcpyDeviceToHost, st));
+    if (m2_out) HIPCHK(hipMemcpyAsync(m2_out, m2, n * 12, hipMemcpyDeviceToHost, st));
+    if (layers_out) HIPCHK(hipMemcpyAsync(layers_out, map, n * 4, hipMemcpyDeviceToHost, st));
+    if (owner_out) HIPCHK(hipMemcpyAsync(owner_out, owner, n * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (stats_out) *stats_out = out;
     return CR_OK;
 }
 

@@ -75,6 +75,13 @@ struct cr_ctx : cr::CtxOptions { // (the options, cr_set_option's table: ctxopts
     bool tp_has = false;
     uint32_t tp_side = 0, tp_x = 0, tp_y = 0;
     cr_camera tp_cam{};
+    // lightmap baking (cr_bake_dilate_device / cr_bake), grow-only: the dilation's level map; cr_bake's surface
+    // (owner, pos, nrm, the covered list and its count), its two frames, layer map and active lists.  bake_ev is
+    // recorded after each dilation: one on another stream than the last waits for it, one that regrows synchronises
+    crx::DevBuf d_bake_level, d_bake;
+    crx::Event bake_ev;
+    bool bake_pending = false;
+    hipStream_t bake_stream = nullptr;
     crx::DevBuf d_cull;      // camera-ray cull boxes, one per leaf reference (+ 4), per render
     crx::DevBuf d_cull_node; // ... their per-leaf unions, one per kd node
     cr_counters last{};

@@ -211,6 +211,34 @@ int launch_tile_list(uint32_t xres, uint32_t yres, uint32_t tile, uint32_t *out,
 // map[list[i]] = value for the n entries of list that are pixels (list null: map[i] = value for i < n)
 int launch_list_fill(uint32_t *map, const uint32_t *list, uint32_t n, uint32_t npix, uint32_t value, hipStream_t st);
 
+// texbake.hip: the texture-space side of a lightmap bake (cr_bake_surface_device / cr_bake_dilate_device;
+// include/chiaro_hip.h "lightmap baking"; the arithmetic: bake.hpp).
+// launch_bake_surface: owner preset to BAKE_NONE, the owner pass (a wave per triangle, atomicMin of the id), the
+// surface pass (a thread per texel: pos / nrm, zeros where unowned) and the order-keeping compaction of the owned
+// texels into list, their count into *count, through `scratch` [SELECT_SCRATCH] uint32 as the selection's.
+struct BakeArgs {
+    const float4 *tri;   // DevScene::tri, 3 per triangle
+    const float4 *mat_n; // DevScene::mat_n
+    const float *uv;     // [n_tris][6] lightmap UVs
+    uint32_t n_tris, W, H, npix;
+    float offset;
+    uint32_t *owner;     // [H][W]
+    float *pos, *nrm;    // [H][W][3]
+    uint32_t *list, *count;
+    uint32_t *scratch;   // [SELECT_SCRATCH]
+    uint32_t per_block;  // texels per block of the compaction, a multiple of 256 (the launcher's)
+};
+int launch_bake_surface(BakeArgs B, hipStream_t st);
+// launch_bake_dilate: out = in, then `passes` passes over the level map (null when passes == 0: a copy)
+struct DilateArgs {
+    uint32_t W, H;
+    const uint32_t *owner; // [H][W]
+    uint32_t *level;       // [H][W] scratch
+    const float *in;       // [H][W][3]
+    float *out;
+};
+int launch_bake_dilate(const DilateArgs &D, uint32_t passes, hipStream_t st);
+
 // denoise.hip: the guide buffers of the first hit and the a-trous filter (cr_guides_device / cr_denoise_device;
 // include/chiaro_hip.h "guide buffers and denoiser").
 // guide_rays writes one ray per pixel, through the pixel centre, into orig / dir [npix][3]; the batch then goes

@@ -22,6 +22,15 @@ inline const char *rad_check(uint32_t n, bool arrays, bool have_params, uint32_t
     return nullptr;
 }
 
+// ... and what the list forms add (cr_radiance_list_device / cr_gather_list_device), after rad_check: the arrays are
+// the n x 1 frame of a list pass, so n is bounded as a frame's pixels are
+inline const char *rad_check_list(uint32_t n, uint32_t n_list, bool have_list) {
+    if (n_list && !have_list) return "null list";
+    if (n_list > (1u << 31)) return "list too long";
+    if (n > (1u << 31)) return "a list call's arrays hold at most 2^31 entries";
+    return nullptr;
+}
+
 // A ray pass: entries [first, first + count) of the call's arrays as an n x 1 "frame" of `count` pixels whose work
 // items are `items` (the entries padded to whole tiles); entry e of the pass draws from stream id0 + e and its
 // arrays start `first` rays into the caller's (3 * first floats).

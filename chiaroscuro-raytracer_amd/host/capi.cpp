@@ -388,6 +388,29 @@ int chiaro_raytracer_gather(chiaro_raytracer *r, const float *pos, const float *
         },
         CR_E_HIP);
 }
+int chiaro_raytracer_bake(chiaro_raytracer *r, uint32_t width, uint32_t height, const float *uv, uint32_t layers,
+                          uint32_t dilate, float *lightmap_out, float *dilated_out) {
+    if (!r || !width || !height || layers < 1 || !lightmap_out) return CR_E_INVALID;
+    return guard(
+        [&]() -> int {
+            r->r->bakeLightmap(width, height, uv, layers, dilate, lightmap_out, dilated_out);
+            return CR_OK;
+        },
+        CR_E_HIP);
+}
+int chiaro_raytracer_bake_adaptive(chiaro_raytracer *r, uint32_t width, uint32_t height, const float *uv,
+                                   float threshold, uint32_t max_layers, float floor, uint32_t min_layers,
+                                   uint32_t check_every, uint32_t dilate, float *lightmap_out, float *dilated_out,
+                                   uint32_t *layers_out) {
+    if (!r || !width || !height || max_layers < 1 || !lightmap_out) return CR_E_INVALID;
+    return guard(
+        [&]() -> int {
+            r->r->bakeLightmap(width, height, uv, threshold, max_layers, floor, min_layers, check_every, dilate,
+                               lightmap_out, dilated_out, layers_out);
+            return CR_OK;
+        },
+        CR_E_HIP);
+}
 int chiaro_raytracer_count_map(const chiaro_raytracer *r, uint32_t *counts_out) {
     if (!r || !counts_out || r->r->countMap().empty()) return CR_E_INVALID;
     std::memcpy(counts_out, r->r->countMap().data(), r->r->countMap().size() * sizeof(uint32_t));

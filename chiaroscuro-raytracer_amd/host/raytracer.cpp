@@ -360,6 +360,59 @@ void RayTracer::gather(const float *pos, const float *nrm, uint32_t n, unsigned 
     cr_get_counters(ctx_, &counters_);
 }
 
+// bakeLightmap(): cr_bake with the Scene's sampling; uv null: the grid atlas at the largest cell that fits
+static cr_bake_stats bake_with(cr_ctx *ctx, const Scene &scene, size_t n_tris, uint32_t W, uint32_t H, const float *uv,
+                               unsigned layers, const cr_adaptive_params *ap, const cr_noise_params *np, unsigned dilate,
+                               float *out, float *dilated, uint32_t *layersOut) {
+    cr_bake_params p;
+    cr_bake_params_default(&p);
+    p.width = W, p.height = H;
+    p.spp = scene.samples;
+    p.k = scene.k;
+    p.background[0] = scene.background.x;
+    p.background[1] = scene.background.y;
+    p.background[2] = scene.background.z;
+    p.seed = scene.seed;
+    std::vector<float> atlas;
+    if (!uv) {
+        uint32_t w1 = 0, h1 = 0;
+        if (!n_tris || cr_bake_atlas_grid((uint32_t)n_tris, 1, 0.25f, &w1, &h1, nullptr) != CR_OK || !w1 || !h1)
+            throw std::runtime_error("chiaro: bakeLightmap: no triangles for a grid atlas");
+        const uint32_t cell = std::min(W / w1, H / h1); // (at cell 1 the atlas is cols x rows texels)
+        if (!cell) throw std::runtime_error("chiaro: bakeLightmap: the map is smaller than one texel per triangle");
+        atlas.resize(6 * n_tris);
+        if (cr_bake_atlas_grid((uint32_t)n_tris, cell, 0.25f, &w1, &h1, atlas.data()) != CR_OK)
+            throw std::runtime_error("chiaro: bakeLightmap: grid atlas failed");
+        const float sx = (float)w1 / (float)W, sy = (float)h1 / (float)H;
+        if (w1 != W || h1 != H)
+            for (size_t i = 0; i < atlas.size(); i += 2) atlas[i] *= sx, atlas[i + 1] *= sy;
+        uv = atlas.data();
+    }
+    cr_bake_stats st{};
+    if (cr_bake(ctx, &p, uv, layers, ap, np, dilate, out, nullptr, layersOut, nullptr, dilated, &st) != CR_OK)
+        throw std::runtime_error(std::string("chiaro: bakeLightmap failed: ") + cr_last_error(ctx));
+    return st;
+}
+cr_bake_stats RayTracer::bakeLightmap(uint32_t W, uint32_t H, const float *uv, unsigned layers, unsigned dilate,
+                                      float *out, float *dilated) {
+    if (group_) throw std::runtime_error("chiaro: bakeLightmap runs on one GPU (gpus 1)");
+    const cr_bake_stats st = bake_with(ctx_, scene, kdtree.triangles.size(), W, H, uv, layers, nullptr, nullptr, dilate,
+                                       out, dilated, nullptr);
+    cr_get_counters(ctx_, &counters_);
+    return st;
+}
+cr_bake_stats RayTracer::bakeLightmap(uint32_t W, uint32_t H, const float *uv, float threshold, unsigned maxLayers,
+                                      float floor, unsigned minLayers, unsigned checkEvery, unsigned dilate, float *out,
+                                      float *dilated, uint32_t *layersOut) {
+    if (group_) throw std::runtime_error("chiaro: bakeLightmap runs on one GPU (gpus 1)");
+    const cr_noise_params np{threshold, floor};
+    const cr_adaptive_params ap{minLayers, maxLayers, checkEvery};
+    const cr_bake_stats st = bake_with(ctx_, scene, kdtree.triangles.size(), W, H, uv, 0, &ap, &np, dilate, out, dilated,
+                                       layersOut);
+    cr_get_counters(ctx_, &counters_);
+    return st;
+}
+
 void RayTracer::resetTemporal() {
     if (group_) return; // (no history with gpus > 1)
     if (cr_temporal_reset(ctx_) != CR_OK)

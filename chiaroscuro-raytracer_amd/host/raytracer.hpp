@@ -85,6 +85,21 @@ class RayTracer {
      * temporal history are untouched.  One GPU only. */
     void radiance(const float *orig, const float *dir, uint32_t n, unsigned layers, float *out);
     void gather(const float *pos, const float *nrm, uint32_t n, unsigned layers, float *out);
+    /* This build: lightmap baking (cr_bake, include/chiaro_hip.h "lightmap baking").  The W x H lightmap over the
+     * lightmap UVs uv ([triangles][6], the scene's triangle order): the mean incoming radiance under the cosine
+     * density at the surface point under each covered texel's centre (times pi and the albedo: the caller's), texel
+     * y * W + x on the stream of pixel index y * W + x, `layers` layers of scene.samples samples with scene.k,
+     * scene.background and scene.seed.  uv null: the grid atlas of the scene's triangles (cr_bake_atlas_grid, gutter
+     * 0.25) with the largest cell that fits W x H, in the map's top-left corner.  out [H][W][3]; dilated
+     * [H][W][3], when given, is out after `dilate` gutter-filling passes.  The adaptive overload renders further
+     * layers only for the texels whose error is above threshold (rayTraceAdaptive's parameters) and returns the
+     * (texel, layer) pairs rendered; layersOut [H][W] may be null.  The frame, the progressive state and the temporal
+     * history are untouched.  One GPU only, no back faces. */
+    cr_bake_stats bakeLightmap(uint32_t W, uint32_t H, const float *uv, unsigned layers, unsigned dilate, float *out,
+                               float *dilated = nullptr);
+    cr_bake_stats bakeLightmap(uint32_t W, uint32_t H, const float *uv, float threshold, unsigned maxLayers, float floor,
+                               unsigned minLayers, unsigned checkEvery, unsigned dilate, float *out,
+                               float *dilated = nullptr, uint32_t *layersOut = nullptr);
     /* The statistic of the last rayTraceUntil's last check, and the error map [yres][xres] of its frame. */
     const cr_noise_stats &lastNoise() const { return noise_; }
     std::vector<float> noiseMap();

@@ -58,6 +58,11 @@
  *                        RayTracer::sendRay (src/rayTracer.cpp:76-135) along caller rays, or along directions drawn
  *                        about caller normals, with a frame pixel's sample loop and blend (:59-64) per ray (no
  *                        reference counterpart as an entry: its only caller of sendRay is the camera loop, :58-62).
+ *   cr_radiance_list_device / cr_gather_list_device
+ *                        the same for the listed entries of the arrays alone.
+ *   cr_bake_surface_device / cr_bake_dilate_device / cr_bake_atlas_grid / cr_bake
+ *                        lightmap baking: the surface point under each texel of a second UV set, cr_gather over the
+ *                        covered texels (fixed or adaptive), gutter dilation (no reference counterpart).
  *
  * Threading: one cr_ctx per GPU, not thread-safe; calls on one ctx are serialised.
  */
@@ -669,6 +674,102 @@ int cr_radiance(cr_ctx *ctx, uint32_t n, const float *orig, const float *dir, co
                 uint32_t nlayers, float *out, float *m2 /* may be null */);
 int cr_gather(cr_ctx *ctx, uint32_t n, const float *pos, const float *nrm, const cr_radiance_params *p,
               uint32_t nlayers, float *out, float *m2 /* may be null */);
+/* LIST FORMS.  The arrays have n entries; d_list [n_list] is a pixel list in the sense of the adaptive block above:
+ * distinct entries, 0xffffffff a skipped entry, an index >= n skipped.  Listed entry e is ray e of
+ * cr_radiance_device / cr_gather_device -- stream id p->id0 + e -- and layers p->layer .. p->layer + nlayers - 1 are
+ * blended in place into d_out[e] (and d_m2[e]); no other entry of either array is read or written.  A listed entry
+ * then holds, bit for bit, what the non-list call over all n entries leaves there.  The pass is a list pass
+ * (cr_render_layers_list_device) over the n x 1 frame with the caller's rays: batches, binding and the refusal of
+ * "perf_counters" 1 are those of the calls above.  n_list == 0: CR_OK, nothing launched.
+ * Errors: those of the calls above; a null d_list with n_list > 0, n_list above 2^31 or n above 2^31 (the frame). */
+int cr_radiance_list_device(cr_ctx *ctx, uint32_t n, const float *d_orig, const float *d_dir, const uint32_t *d_list,
+                            uint32_t n_list, const cr_radiance_params *p, uint32_t nlayers, float *d_out,
+                            float *d_m2 /* may be null */, void *stream);
+int cr_gather_list_device(cr_ctx *ctx, uint32_t n, const float *d_pos, const float *d_nrm, const uint32_t *d_list,
+                          uint32_t n_list, const cr_radiance_params *p, uint32_t nlayers, float *d_out,
+                          float *d_m2 /* may be null */, void *stream);
+
+/* ---- lightmap baking: texture-space surface points, gathers over them, dilation ----
+ * A lightmap is a W x H map over the scene's triangles in a second UV set.  It is treated as a W*H x 1 frame: texel
+ * t = y * W + x gathers (cr_gather) at the surface point under its centre and draws from stream t, whatever other
+ * texels are covered.  Everything below is float32, the operations in the order written, no contraction.
+ *
+ * INPUTS.  W, H >= 1, W * H <= 2^31.  d_uv [n_tris][6]: the lightmap UVs (u0 v0 u1 v1 u2 v2) of each scene triangle,
+ * in the scene's triangle order; null: the scene's own tri_uv.
+ *
+ * COVERAGE.  Texel-space vertices q_k = (u_k * (float)W, v_k * (float)H); texel (x, y) has centre
+ * c = ((float)x + 0.5, (float)y + 0.5); edge(a, b, c) = (b.x - a.x) * (c.y - a.y) - (b.y - a.y) * (c.x - a.x).
+ * A = edge(q0, q1, q2).  If A == 0, or any of the six UVs is not finite, the triangle covers nothing.  Otherwise
+ * w0 = edge(q1, q2, c), w1 = edge(q2, q0, c), w2 = edge(q0, q1, c) (the weights of q0, q1, q2); when A < 0 all four
+ * are negated.  The texel is covered iff w0 >= 0 && w1 >= 0 && w2 >= 0 -- inclusive, so a shared edge loses no
+ * texel -- and c lies in the triangle's bounding box, min_k q_k <= c <= max_k q_k per axis (inclusive; exact
+ * comparisons, which make the box the owner pass walks part of the definition rather than of its rounding).
+ * OWNER.  d_owner [H][W]: the LOWEST triangle id that covers the texel, 0xffffffff where none does.
+ * SURFACE POINT.  With owner t: b1 = w1 / A, b2 = w2 / A, b0 = 1 - b1 - b2, P = (p0 * b0 + p1 * b1) + p2 * b2 per
+ * component, nrm = tri_normal[t] + 0.0f, pos = P + offset * nrm.  Unowned texels hold zeros in d_pos / d_nrm
+ * [H][W][3].  No back faces: the normal is the triangle's own.
+ * COVERED LIST.  d_list (room W * H): the owned texel indices ascending; *d_count their number (a device word).
+ *
+ * cr_bake_surface_device reads width, height and offset of the params; it is stream-ordered, does not synchronise
+ * the host, and uses the ctx's selection scratch under cr_noise_select_device's rule.
+ * Errors (arguments, then the device, then the scene): CR_E_INVALID for a null pointer (d_uv may be null), W or H
+ * 0, W * H > 2^31, an offset that is not finite; CR_E_NOSCENE. */
+typedef struct cr_bake_params {
+    uint32_t width, height; /* the map */
+    uint32_t spp;           /* samples per layer */
+    int32_t k;              /* max path depth, 1..64 */
+    float background[3];
+    uint32_t seed;
+    float offset;           /* the point's distance off the surface along the normal; the integrator's own: 0.001 */
+} cr_bake_params;
+typedef struct cr_bake_stats {
+    uint64_t covered;      /* owned texels */
+    uint64_t texel_layers; /* (texel, layer) pairs rendered */
+    uint64_t active;       /* `above` of the last check (0 if none ran) */
+    uint32_t layers;       /* the last layer rendered */
+    uint32_t checks;       /* checks run */
+    float max_err;         /* of the last check (0 if none ran) */
+    uint32_t reserved;
+} cr_bake_stats;
+/* {0, 0, 1, 6, {0, 0, 0}, 0, 0.001f} */
+void cr_bake_params_default(cr_bake_params *out);
+void cr_bake_struct_sizes(uint32_t *params_bytes, uint32_t *stats_bytes);
+int cr_bake_surface_device(cr_ctx *ctx, const cr_bake_params *p, const float *d_uv /* may be null */,
+                           uint32_t *d_owner, float *d_pos, float *d_nrm, uint32_t *d_list, uint32_t *d_count,
+                           void *stream);
+/* DILATION.  A texel is "filled" if it is owned (d_owner != 0xffffffff) or an earlier pass filled it.  In each of
+ * `passes` passes every unfilled texel with at least one filled 8-neighbour becomes (the sum of those neighbours'
+ * values) / (float)count, the neighbours summed from 0 in the order (-1,0), (+1,0), (0,-1), (0,+1), (-1,-1), (+1,-1),
+ * (-1,+1), (+1,+1) ((dx, dy), inside the map); a pass reads only the state the previous pass left.  Owned texels, and
+ * texels no pass reaches, are copied through; passes == 0 is a copy.  d_in / d_out [H][W][3] must not alias.  Needs no
+ * scene.  Stream-ordered; a call that has to grow the ctx's level map first waits for the last dilation.
+ * Errors: CR_E_INVALID for a null pointer, W or H 0, W * H > 2^31, d_in == d_out. */
+int cr_bake_dilate_device(cr_ctx *ctx, uint32_t W, uint32_t H, const uint32_t *d_owner, uint32_t passes,
+                          const float *d_in, float *d_out, void *stream);
+/* THE GRID ATLAS, for a mesh without an unwrap: triangle t in cell (t % cols, t / cols) of a
+ * cols = ceil(sqrt(n_tris)) grid of cell x cell texels, W = cols * cell, H = ceil(n_tris / cols) * cell, its vertices
+ * at texel offsets (g, g), (cell - g, g), (g, cell - g) of its cell divided by (float)W, (float)H; g = gutter, by
+ * convention 0.25.  uv_out [n_tris][6] may be null (the size only).  Needs no device.  CR_E_INVALID: n_tris or cell
+ * 0, gutter outside [0, cell / 2), W * H > 2^31. */
+int cr_bake_atlas_grid(uint32_t n_tris, uint32_t cell, float gutter, uint32_t *W_out, uint32_t *H_out, float *uv_out);
+/* THE BAKE.  (1) the surface of uv (host [n_tris][6], null: the scene's tri_uv); (2) cr_gather over the covered list
+ * with id0 = 0 -- texel t is stream t -- and layer 1 first; (3) `dilate` passes of the lightmap into dilated_out when
+ * that is given.  ap == NULL: nlayers layers for every covered texel.  ap given (nlayers ignored): cr_render_adaptive's
+ * loop, word for word, over the W*H x 1 frame -- steps of ad_step's schedule, the covered list the first active set,
+ * each check cr_noise_select_device over the active list with np, the selected texels the next active set, texels
+ * that drop out frozen at the layers they hold.  np is read in adaptive mode only.
+ * lightmap_out [H][W][3]: the MEAN INCOMING RADIANCE under the cosine density, as cr_gather returns it; the
+ * multiplication by pi and by albedo is the caller's, and the light the texel's own surface emits is not in it.
+ * m2_out: the moment frame beside it -- (lightmap_out, m2_out) is a valid W*H x 1 frame for cr_noise*.  layers_out
+ * [H][W]: the layers each texel holds (0 where uncovered).  owner_out [H][W].  Uncovered texels are zero in the two
+ * frames.  The last five outputs may be null.  The ctx's accumulators, adaptive state and temporal history are
+ * untouched.  Returns when complete.
+ * Errors (arguments, then the device, then the scene): CR_E_INVALID for null params / lightmap_out, a bad map or
+ * offset, spp == 0, k outside 1..64, no layers, (adaptive) the errors of cr_render_adaptive's parameters. */
+int cr_bake(cr_ctx *ctx, const cr_bake_params *p, const float *uv /* host, may be null */, uint32_t nlayers,
+            const cr_adaptive_params *ap /* may be null */, const cr_noise_params *np, uint32_t dilate,
+            float *lightmap_out, float *m2_out, uint32_t *layers_out, uint32_t *owner_out, float *dilated_out,
+            cr_bake_stats *stats_out);
 
 int cr_get_counters(cr_ctx *ctx, cr_counters *out);
 /* Device time (ms) of the last render kernel, HIP events on its own stream. */

@@ -18,6 +18,8 @@
  *   chiaro_raytracer_radiance / _gather
  *                            RayTracer::sendRay (src/rayTracer.cpp:76-135) along caller rays (this build; cr_radiance,
  *                            cr_gather)
+ *   chiaro_raytracer_bake / _bake_adaptive
+ *                            a lightmap of the scene in a second UV set (this build; cr_bake)
  *   chiaro_raytracer_raytrace_until / _noise / _noise_map
  *                            rayTrace repeated until a noise target is met (this build; the accumulation of
  *                            src/rayTracer.cpp:18-33,59-64 with a second-moment frame, cr_render_until)
@@ -152,6 +154,22 @@ int chiaro_raytracer_radiance(chiaro_raytracer *r, const float *orig, const floa
                               float *out);
 int chiaro_raytracer_gather(chiaro_raytracer *r, const float *pos, const float *nrm, uint32_t n, uint32_t layers,
                             float *out);
+/* RayTracer::bakeLightmap (cr_bake, include/chiaro_hip.h "lightmap baking"): the width x height lightmap over the
+ * lightmap UVs uv ([triangles][6] in the scene's triangle order; null: the grid atlas of the scene's triangles at the
+ * largest cell that fits, gutter 0.25, in the map's top-left corner) -- the mean incoming radiance under the cosine
+ * density at each covered texel (times pi and the albedo: the caller's), texel y * width + x on the stream of pixel
+ * index y * width + x, with the Scene's samples, k, background and seed.  lightmap_out [height][width][3];
+ * dilated_out (may be null) the map after `dilate` gutter-filling passes.  _bake renders `layers` layers for every
+ * covered texel; _bake_adaptive further layers only where the error is above threshold (the parameters of
+ * chiaro_raytracer_raytrace_adaptive), layers_out [height][width] (may be null) the layers each texel holds.
+ * CR_E_INVALID for a null handle or output, a zero size or no layers; CR_E_HIP with chiaro_last_error otherwise.
+ * One GPU only. */
+int chiaro_raytracer_bake(chiaro_raytracer *r, uint32_t width, uint32_t height, const float *uv, uint32_t layers,
+                          uint32_t dilate, float *lightmap_out, float *dilated_out);
+int chiaro_raytracer_bake_adaptive(chiaro_raytracer *r, uint32_t width, uint32_t height, const float *uv,
+                                   float threshold, uint32_t max_layers, float floor, uint32_t min_layers,
+                                   uint32_t check_every, uint32_t dilate, float *lightmap_out, float *dilated_out,
+                                   uint32_t *layers_out);
 const float *chiaro_raytracer_pixels(const chiaro_raytracer *r);
 const uint8_t *chiaro_raytracer_data(chiaro_raytracer *r);
 float chiaro_raytracer_maxval(const chiaro_raytracer *r);
