@@ -281,6 +281,30 @@ def bake_atlas_grid(n_tris: int, cell: int, gutter: float = 0.25):
     return int(w.value), int(h.value), uv
 
 
+class CrProbeGrid(C.Structure):
+    """cr_probe_grid (include/chiaro_hip.h "probes")."""
+    _fields_ = [("origin", C.c_float * 3), ("step", C.c_float * 3), ("dims", C.c_uint32 * 3)]
+
+    @property
+    def count(self) -> int:
+        return int(self.dims[0]) * int(self.dims[1]) * int(self.dims[2])
+
+
+def probe_grid(origin, step, dims) -> CrProbeGrid:
+    """A cr_probe_grid: probe (x, y, z) has index (z * ny + y) * nx + x and sits at origin + (x, y, z) * step."""
+    return CrProbeGrid((C.c_float * 3)(*[float(v) for v in origin]), (C.c_float * 3)(*[float(v) for v in step]),
+                       (C.c_uint32 * 3)(*[int(v) for v in dims]))
+
+
+def probe_grid_positions(grid: CrProbeGrid) -> np.ndarray:
+    """cr_probe_grid_positions: the probes' positions [count][3] float32 in index order.  Needs no device."""
+    pos = np.zeros((max(grid.count, 1), 3), np.float32)
+    rc = libs()[0].cr_probe_grid_positions(C.byref(grid), _ptr(pos))
+    if rc:
+        raise RuntimeError("cr_probe_grid_positions: %s" % CR_ERRORS.get(rc, rc))
+    return pos[:grid.count]
+
+
 def temporal_params(depth_tol=None, normal_min=None, max_history=None) -> CrTemporalParams:
     """cr_temporal_params_default (0.05, 0.9, 65536) with the given fields replaced."""
     tp = CrTemporalParams()
@@ -324,7 +348,9 @@ HIP_SYMBOLS = ("cr_create", "cr_destroy", "cr_last_error", "cr_upload_scene", "c
                "cr_temporal_reset", "cr_temporal_history",
                "cr_radiance_struct_sizes", "cr_radiance_device", "cr_gather_device", "cr_radiance", "cr_gather",
                "cr_radiance_list_device", "cr_gather_list_device", "cr_bake_params_default", "cr_bake_struct_sizes",
-               "cr_bake_surface_device", "cr_bake_dilate_device", "cr_bake_atlas_grid", "cr_bake")
+               "cr_bake_surface_device", "cr_bake_dilate_device", "cr_bake_atlas_grid", "cr_bake",
+               "cr_probe_struct_sizes", "cr_probe_grid_positions", "cr_probe_sh_device", "cr_probe_sh",
+               "cr_probe_eval_device", "cr_probe_sample_device", "cr_probe_eval", "cr_probe_sample")
 HOST_SYMBOLS = ("chiaro_last_error", "chiaro_scene_create", "chiaro_scene_info_get", "chiaro_scene_destroy",
                 "chiaro_model_create", "chiaro_model_load", "chiaro_model_num_meshes", "chiaro_model_num_triangles",
                 "chiaro_model_num_textures", "chiaro_model_triangles", "chiaro_model_texture",
@@ -345,7 +371,8 @@ HOST_SYMBOLS = ("chiaro_last_error", "chiaro_scene_create", "chiaro_scene_info_g
                 "chiaro_raytracer_adaptive", "chiaro_raytracer_layer_map", "chiaro_raytracer_denoise",
                 "chiaro_raytracer_denoised", "chiaro_raytracer_raytrace_temporal", "chiaro_raytracer_reset_temporal",
                 "chiaro_raytracer_count_map", "chiaro_preview_set_temporal", "chiaro_raytracer_radiance",
-                "chiaro_raytracer_gather", "chiaro_raytracer_bake", "chiaro_raytracer_bake_adaptive")
+                "chiaro_raytracer_gather", "chiaro_raytracer_bake", "chiaro_raytracer_bake_adaptive",
+                "chiaro_raytracer_probes", "chiaro_raytracer_probes_sample")
 
 P = C.c_void_p
 FP = C.POINTER(C.c_float)
@@ -497,6 +524,15 @@ def libs():
     _sig(hip, "cr_bake_atlas_grid", C.c_int, [C.c_uint32, C.c_uint32, C.c_float, UP, UP, FP])
     _sig(hip, "cr_bake", C.c_int, [CTX, BP, FP, C.c_uint32, C.POINTER(CrAdaptiveParams), C.POINTER(CrNoiseParams),
                                    C.c_uint32, FP, FP, UP, UP, FP, C.POINTER(CrBakeStats)])
+    GP = C.POINTER(CrProbeGrid)
+    _sig(hip, "cr_probe_struct_sizes", None, [UP])
+    _sig(hip, "cr_probe_grid_positions", C.c_int, [GP, FP])
+    _sig(hip, "cr_probe_sh_device", C.c_int, [CTX, C.c_uint32, P, RP, C.c_uint32, P, P, P])
+    _sig(hip, "cr_probe_sh", C.c_int, [CTX, C.c_uint32, FP, RP, C.c_uint32, FP, FP])
+    _sig(hip, "cr_probe_eval_device", C.c_int, [CTX, C.c_uint32, P, P, P, P, P])
+    _sig(hip, "cr_probe_sample_device", C.c_int, [CTX, GP, P, C.c_uint32, P, P, P, P])
+    _sig(hip, "cr_probe_eval", C.c_int, [CTX, C.c_uint32, FP, C.c_uint32, UP, FP, FP])
+    _sig(hip, "cr_probe_sample", C.c_int, [CTX, GP, FP, C.c_uint32, FP, FP, FP])
 
     _sig(host, "chiaro_last_error", C.c_char_p, [])
     _sig(host, "chiaro_scene_create", P, [C.c_int, C.POINTER(C.c_char_p)])
@@ -538,6 +574,8 @@ def libs():
     _sig(host, "chiaro_preview_set_temporal", C.c_int, [P, C.c_int])
     _sig(host, "chiaro_raytracer_radiance", C.c_int, [P, FP, FP, C.c_uint32, C.c_uint32, FP])
     _sig(host, "chiaro_raytracer_gather", C.c_int, [P, FP, FP, C.c_uint32, C.c_uint32, FP])
+    _sig(host, "chiaro_raytracer_probes", C.c_int, [P, GP, FP, C.c_uint32, C.c_uint32, FP])
+    _sig(host, "chiaro_raytracer_probes_sample", C.c_int, [P, GP, FP, FP, FP, C.c_uint32, FP])
     _sig(host, "chiaro_raytracer_bake", C.c_int, [P, C.c_uint32, C.c_uint32, FP, C.c_uint32, C.c_uint32, FP, FP])
     _sig(host, "chiaro_raytracer_bake_adaptive", C.c_int, [P, C.c_uint32, C.c_uint32, FP, C.c_float, C.c_uint32,
                                                            C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, FP, FP, UP])
@@ -1069,6 +1107,66 @@ class Device:
                                                   C.c_void_p(d_out_ptr or None), C.c_void_p(d_m2_ptr or None),
                                                   C.c_void_p(stream)), "cr_gather_list_device")
 
+    def probe_sh_device(self, n: int, d_pos_ptr: int, rp: CrRadianceParams, nlayers: int, d_sh_ptr: int,
+                        d_m2_ptr: int = 0, stream: int = 0):
+        """cr_probe_sh_device: layers rp.layer .. + nlayers - 1 of the order-2 SH projection of the light arriving at
+        n device points ([n][3] float; probe i draws from stream rp.id0 + i), blended into the device arrays d_sh
+        [n][27] (sh[i][k][c]) and, when given, d_m2 [n][27].  Returns when complete."""
+        self._chk(libs()[0].cr_probe_sh_device(self._c, int(n), C.c_void_p(d_pos_ptr or None), C.byref(rp),
+                                               int(nlayers), C.c_void_p(d_sh_ptr or None),
+                                               C.c_void_p(d_m2_ptr or None), C.c_void_p(stream)), "cr_probe_sh_device")
+
+    def probe_sh(self, pos, rp: CrRadianceParams, nlayers: int = 1, sh=None, m2=None) -> np.ndarray:
+        """cr_probe_sh on host arrays; sh / m2 ([n][9][3] float32) are read for rp.layer > 1 and written."""
+        pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+        n = len(pos)
+        sh = np.zeros((n, 9, 3), np.float32) if sh is None else sh
+        for a in (sh, m2):
+            assert a is None or (a.dtype == np.float32 and a.flags.c_contiguous and a.size == 27 * n)
+        self._chk(libs()[0].cr_probe_sh(self._c, n, _ptr(pos), C.byref(rp), int(nlayers), _ptr(sh),
+                                        _ptr(m2) if m2 is not None else None), "cr_probe_sh")
+        return sh
+
+    def probe_eval_device(self, m: int, d_sh_ptr: int, d_probe_ptr: int, d_nrm_ptr: int, d_out_ptr: int,
+                          stream: int = 0):
+        """cr_probe_eval_device: d_out[j] ([m][3]) = the mean incoming radiance under the cosine density about
+        d_nrm[j] from the coefficients of probe d_probe[j] (uint32) of d_sh.  Stream-ordered."""
+        self._chk(libs()[0].cr_probe_eval_device(self._c, int(m), C.c_void_p(d_sh_ptr or None),
+                                                 C.c_void_p(d_probe_ptr or None), C.c_void_p(d_nrm_ptr or None),
+                                                 C.c_void_p(d_out_ptr or None), C.c_void_p(stream)),
+                  "cr_probe_eval_device")
+
+    def probe_sample_device(self, grid: CrProbeGrid, d_sh_ptr: int, m: int, d_pos_ptr: int, d_nrm_ptr: int,
+                            d_out_ptr: int, stream: int = 0):
+        """cr_probe_sample_device: d_out[j] ([m][3]) = probe_eval_device's quantity at d_pos[j] for d_nrm[j] from the
+        grid's coefficients d_sh [count][27], trilinearly interpolated (clamped outside).  Stream-ordered."""
+        self._chk(libs()[0].cr_probe_sample_device(self._c, C.byref(grid), C.c_void_p(d_sh_ptr or None), int(m),
+                                                   C.c_void_p(d_pos_ptr or None), C.c_void_p(d_nrm_ptr or None),
+                                                   C.c_void_p(d_out_ptr or None), C.c_void_p(stream)),
+                  "cr_probe_sample_device")
+
+    def probe_eval(self, sh, probe, nrm) -> np.ndarray:
+        """cr_probe_eval on host arrays: sh [n][9][3], probe [m] indices, nrm [m][3] -> [m][3]."""
+        sh = np.ascontiguousarray(sh, np.float32).reshape(-1, 27)
+        probe = np.ascontiguousarray(probe, np.uint32)
+        nrm = np.ascontiguousarray(nrm, np.float32).reshape(-1, 3)
+        assert len(nrm) == len(probe)
+        out = np.zeros((len(probe), 3), np.float32)
+        self._chk(libs()[0].cr_probe_eval(self._c, len(sh), _ptr(sh), len(probe), _ptr(probe, C.c_uint32), _ptr(nrm),
+                                          _ptr(out)), "cr_probe_eval")
+        return out
+
+    def probe_sample(self, grid: CrProbeGrid, sh, pos, nrm) -> np.ndarray:
+        """cr_probe_sample on host arrays: sh [count][9][3] of the grid, pos / nrm [m][3] -> [m][3]."""
+        sh = np.ascontiguousarray(sh, np.float32).reshape(-1, 27)
+        pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+        nrm = np.ascontiguousarray(nrm, np.float32).reshape(-1, 3)
+        assert len(sh) == grid.count and len(pos) == len(nrm)
+        out = np.zeros((len(pos), 3), np.float32)
+        self._chk(libs()[0].cr_probe_sample(self._c, C.byref(grid), _ptr(sh), len(pos), _ptr(pos), _ptr(nrm),
+                                            _ptr(out)), "cr_probe_sample")
+        return out
+
     def bake_surface_device(self, bp: CrBakeParams, d_uv_ptr: int, d_owner_ptr: int, d_pos_ptr: int, d_nrm_ptr: int,
                             d_list_ptr: int, d_count_ptr: int, stream: int = 0):
         """cr_bake_surface_device: for the bp.width x bp.height lightmap over the UVs d_uv ([n_tris][6] float, 0: the
@@ -1469,6 +1567,35 @@ class RayTracer:
         """The mean incoming radiance under the cosine density at the points (pos, nrm: [n][3]); irradiance is pi
         times it, and offsetting pos off the surface is the caller's job (cr_gather); [n][3]."""
         return self._radiance(libs()[1].chiaro_raytracer_gather, "gather", pos, nrm, layers)
+
+    def bakeProbes(self, where, layers=1) -> np.ndarray:
+        """The order-2 SH projection of the light arriving at the probes of a CrProbeGrid (in index order) or at the
+        points where ([n][3]): layers 1 .. layers with the Scene's samples, k, background and seed (cr_probe_sh);
+        [n][9][3] = sh[i][k][c].  The frame is untouched."""
+        if isinstance(where, CrProbeGrid):
+            n, grid, pos = where.count, C.byref(where), None
+        else:
+            pos = np.ascontiguousarray(where, np.float32).reshape(-1, 3)
+            n, grid = len(pos), None
+        sh = np.zeros((n, 9, 3), np.float32)
+        if libs()[1].chiaro_raytracer_probes(self._h, grid, _ptr(pos) if pos is not None else None, n, int(layers),
+                                             _ptr(sh)):
+            raise RuntimeError("bakeProbes: " + _host_err())
+        return sh
+
+    def sampleProbes(self, grid: CrProbeGrid, sh, pos, nrm) -> np.ndarray:
+        """The mean incoming radiance under the cosine density (irradiance / pi, what gather returns) at pos for nrm
+        ([m][3] each) from the grid's coefficients sh, trilinearly interpolated, no visibility weighting
+        (cr_probe_sample); [m][3]."""
+        sh = np.ascontiguousarray(sh, np.float32).reshape(-1, 27)
+        pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+        nrm = np.ascontiguousarray(nrm, np.float32).reshape(-1, 3)
+        assert len(sh) == grid.count and len(pos) == len(nrm)
+        out = np.zeros((len(pos), 3), np.float32)
+        if libs()[1].chiaro_raytracer_probes_sample(self._h, C.byref(grid), _ptr(sh), _ptr(pos), _ptr(nrm), len(pos),
+                                                    _ptr(out)):
+            raise RuntimeError("sampleProbes: " + _host_err())
+        return out
 
     def resetTemporal(self):
         if libs()[1].chiaro_raytracer_reset_temporal(self._h):

@@ -7,6 +7,7 @@
 #include "adaptive.hpp"
 #include "bake.hpp"
 #include "denoise.hpp"
+#include "probe.hpp"
 #include "radiance.hpp"
 #include "scenelayout.hpp"
 #include "temporal.hpp"
@@ -197,8 +198,10 @@ cr_counters counters_of(const unsigned long long *h) {
 
 int run_render(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, float *out, int mode, hipStream_t st,
                uint32_t nl, uint32_t piece_k, uint32_t piece_m, uint64_t stride, float *m2, const uint32_t *list,
-               uint32_t list_items, const cr::RaySrc *rays) {
+               uint32_t list_items, const cr::RaySrc *rays, const cr::ShOut *sh) {
     if (!cam || !out) return fail(c, CR_E_INVALID, "null camera/output");
+    if (sh && (!rays || rays->gather != cr::RAY_SRC_SPHERE || m2 || !sh->sh))
+        return fail(c, CR_E_INVALID, "an SH pass is a ray pass in sphere mode with its own moment array");
     if (rays && (!list || c->kernel != 2 || c->perf_counters))
         return fail(c, CR_E_INVALID, "a ray pass is a list pass of the wavefront kernel, without perf_counters");
     if (m2 && mode != cr::MODE_BLEND) return fail(c, CR_E_INVALID, "moments are tracked for blended frames only");
@@ -248,6 +251,16 @@ int run_render(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, float
     if (int r = grow(c, c->d_wf, pl.need_alloc)) return r;
     if (lanes == 2)
         if (int r = grow(c, c->d_wf2, pl.need_alloc)) return r;
+    cr::ShOut H{};
+    if (sh) {
+        H = *sh;
+        if (pl.chunked) { // [n_items][27] running sums, the moments' after them
+            const size_t run_floats = (size_t)A.n_items * cr::PROBE_F;
+            if (int r = grow(c, c->d_probe_run, run_floats * (H.m2 ? 2 : 1) * sizeof(float))) return r;
+            H.run = c->d_probe_run.as<float>();
+            H.run2 = H.m2 ? H.run + run_floats : nullptr;
+        }
+    }
     A.gstack = c->d_gstack.as<uint2>();
     A.samples = c->d_samples.as<float>();
     A.run = c->d_run.as<float>();
@@ -300,8 +313,9 @@ int run_render(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, float
             }
             W.P = P;
         }
-        if (!e) e = cr::launch_sum_samples(A, s0 == 0, s0 + A.s_count == pl.spp_pass, st, c->sum_lds, c->sum_staged != 0,
-                                            m2, c->d_run2.as<float>());
+        if (!e && sh) e = cr::launch_sum_samples_sh(A, s0 == 0, s0 + A.s_count == pl.spp_pass, H, st);
+        else if (!e) e = cr::launch_sum_samples(A, s0 == 0, s0 + A.s_count == pl.spp_pass, st, c->sum_lds, c->sum_staged != 0,
+                                                 m2, c->d_run2.as<float>());
         if (e) return hip_fail(c, (hipError_t)e, "render kernel launch");
     }
     HIPCHK(hipEventRecord(c->ev1, st));
@@ -1430,6 +1444,150 @@ int cr_gather_list_device(cr_ctx *c, uint32_t n, const float *d_pos, const float
                           uint32_t n_list, const cr_radiance_params *p, uint32_t nlayers, float *d_out, float *d_m2,
                           void *stream) {
     return radiance_list_device(c, n, d_pos, d_nrm, true, d_list, n_list, p, nlayers, d_out, d_m2, stream);
+}
+
+// ---- SH irradiance probes (the arithmetic and the checks: probe.hpp) ----
+static_assert(sizeof(cr_probe_grid) == sizeof(cr::ProbeGrid) && offsetof(cr_probe_grid, step) == offsetof(cr::ProbeGrid, step) &&
+                  offsetof(cr_probe_grid, dims) == offsetof(cr::ProbeGrid, dims),
+              "cr_probe_grid is probe.hpp's ProbeGrid");
+static const cr::ProbeGrid *grid_of(const cr_probe_grid *g) { return reinterpret_cast<const cr::ProbeGrid *>(g); }
+void cr_probe_struct_sizes(uint32_t *grid_bytes) {
+    if (grid_bytes) *grid_bytes = (uint32_t)sizeof(cr_probe_grid);
+}
+int cr_probe_grid_positions(const cr_probe_grid *grid, float *pos_out) {
+    if (cr::probe_check_grid(grid_of(grid)) || !pos_out) return CR_E_INVALID;
+    cr::probe_grid_positions(*grid_of(grid), pos_out);
+    return CR_OK;
+}
+// The arguments (rad_check, then probe.hpp probe_check_size), then the device, then the scene
+static int probe_sh_enter(cr_ctx *c, uint32_t n, const void *pos, const cr_radiance_params *p, uint32_t nlayers,
+                          const void *sh) {
+    if (!c) return CR_E_INVALID;
+    const char *msg = cr::rad_check(n, pos && sh, p != nullptr, p ? p->spp : 0, p ? p->k : 0, p ? p->layer : 0,
+                                    p ? p->id0 : 0, nlayers);
+    if (!msg) msg = cr::probe_check_size(n);
+    if (msg) return fail(c, CR_E_INVALID, msg);
+    if (int rc = enter(c)) return rc;
+    if (!c->has_scene) return fail(c, CR_E_NOSCENE, "no scene uploaded");
+    return CR_OK;
+}
+// run_radiance for an SH pass: the ray passes of ad_plan in sphere mode, each projecting into its part of d_sh
+static int run_probe_sh(cr_ctx *c, uint32_t n, const float *d_pos, const cr_radiance_params *p, uint32_t nlayers,
+                        float *d_sh, float *d_m2, hipStream_t st) {
+    const uint32_t max_nl = c->kernel != 2 || c->wf_lanes != 1 || c->full_counters ? 1u : 32u; // (cr_layers_per_pass's rule)
+    const cr::AdPlanIn in = cr::rad_plan_in(n, nlayers, p->spp, max_nl, std::min<uint64_t>(c->wf_paths, wf_path_cap(c, p->k)),
+                                            c->sample_buf);
+    const cr_camera cam{}; // (no kernel of a ray pass reads a camera)
+    PassTotals sum;
+    for (const cr::AdPass &ap : cr::ad_plan(in)) {
+        const cr::RadPass ps = cr::rad_pass(ap, in.tile, p->id0, p->layer);
+        if (int r = grow(c, c->d_list_pad, (size_t)ps.items * sizeof(uint32_t))) return r;
+        if (int e = cr::launch_ray_list(c->d_list_pad.as<uint32_t>(), ps.count, ps.items, st))
+            return hip_fail(c, (hipError_t)e, "ray list kernel launch");
+        cr_render_params t{};
+        t.xres = ps.count, t.yres = 1, t.spp = p->spp, t.k = p->k;
+        std::memcpy(t.background, p->background, sizeof t.background);
+        t.seed = p->seed, t.layer = ps.layer, t.rank = 0, t.nranks = 1, t.tile = in.tile;
+        const float *a = d_pos + 3 * (size_t)ps.first;
+        const cr::RaySrc src{a, a, ps.id0, cr::RAY_SRC_SPHERE};
+        float *sh = d_sh + (size_t)cr::PROBE_F * ps.first;
+        const cr::ShOut out{sh, d_m2 ? d_m2 + (size_t)cr::PROBE_F * ps.first : nullptr, nullptr, nullptr, ps.id0};
+        if (int rc = crx::run_render(c, &cam, &t, sh, cr::MODE_BLEND, st, ps.nl, 0, 1, 0, nullptr,
+                                     c->d_list_pad.as<uint32_t>(), ps.items, &src, &out))
+            return rc;
+        sum.add(c);
+    }
+    sum.store(c);
+    return CR_OK;
+}
+int cr_probe_sh_device(cr_ctx *c, uint32_t n, const float *d_pos, const cr_radiance_params *p, uint32_t nlayers,
+                       float *d_sh, float *d_m2, void *stream) {
+    if (int rc = probe_sh_enter(c, n, d_pos, p, nlayers, d_sh)) return rc;
+    if (n == 0) return CR_OK;
+    return run_probe_sh(c, n, d_pos, p, nlayers, d_sh, d_m2, (hipStream_t)stream);
+}
+int cr_probe_sh(cr_ctx *c, uint32_t n, const float *pos, const cr_radiance_params *p, uint32_t nlayers, float *sh,
+                float *m2) {
+    if (int rc = probe_sh_enter(c, n, pos, p, nlayers, sh)) return rc;
+    if (n == 0) return CR_OK;
+    const size_t pos_bytes = (size_t)n * 3 * sizeof(float), sh_bytes = (size_t)n * cr::PROBE_F * sizeof(float);
+    DevBuf d_p, d_s, d_m;
+    if (int r = grow(c, d_p, pos_bytes, "probe positions")) return r;
+    if (int r = grow(c, d_s, sh_bytes, "probe coefficients")) return r;
+    if (m2)
+        if (int r = grow(c, d_m, sh_bytes, "probe coefficients")) return r;
+    HIPCHK(hipMemcpy(d_p.ptr, pos, pos_bytes, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_s.ptr, sh, sh_bytes, hipMemcpyHostToDevice)); // (layer > 1 blends onto the caller's values)
+    if (m2) HIPCHK(hipMemcpy(d_m.ptr, m2, sh_bytes, hipMemcpyHostToDevice));
+    if (int rc = run_probe_sh(c, n, d_p.as<float>(), p, nlayers, d_s.as<float>(), m2 ? d_m.as<float>() : nullptr, c->stream))
+        return rc;
+    HIPCHK(hipMemcpy(sh, d_s.ptr, sh_bytes, hipMemcpyDeviceToHost));
+    if (m2) HIPCHK(hipMemcpy(m2, d_m.ptr, sh_bytes, hipMemcpyDeviceToHost));
+    return CR_OK;
+}
+int cr_probe_eval_device(cr_ctx *c, uint32_t m, const float *d_sh, const uint32_t *d_probe, const float *d_nrm,
+                         float *d_out, void *stream) {
+    if (!c) return CR_E_INVALID;
+    if (const char *msg = cr::probe_check_eval(m, d_sh && d_probe && d_nrm && d_out, d_sh, 0, d_out))
+        return fail(c, CR_E_INVALID, msg);
+    if (int rc = enter(c)) return rc;
+    if (m == 0) return CR_OK;
+    if (int e = cr::launch_probe_eval(d_sh, d_probe, d_nrm, d_out, m, (hipStream_t)stream))
+        return hip_fail(c, (hipError_t)e, "probe evaluation kernel launch");
+    return CR_OK;
+}
+int cr_probe_sample_device(cr_ctx *c, const cr_probe_grid *grid, const float *d_sh, uint32_t m, const float *d_pos,
+                           const float *d_nrm, float *d_out, void *stream) {
+    if (!c) return CR_E_INVALID;
+    if (const char *msg = cr::probe_check_sample(grid_of(grid), m, d_sh && d_pos && d_nrm && d_out, d_sh, d_out))
+        return fail(c, CR_E_INVALID, msg);
+    if (int rc = enter(c)) return rc;
+    if (m == 0) return CR_OK;
+    if (int e = cr::launch_probe_sample(*grid_of(grid), d_sh, d_pos, d_nrm, d_out, m, (hipStream_t)stream))
+        return hip_fail(c, (hipError_t)e, "probe lookup kernel launch");
+    return CR_OK;
+}
+// the host forms of the two lookups: `first` is the probe indices (eval) or the positions (sample)
+static int probe_lookup_host(cr_ctx *c, const cr_probe_grid *grid, uint64_t n_probes, const float *sh, uint32_t m,
+                             const void *first, const float *nrm, float *out) {
+    const size_t sh_bytes = (size_t)n_probes * cr::PROBE_F * sizeof(float), v_bytes = (size_t)m * 3 * sizeof(float);
+    const size_t first_bytes = grid ? v_bytes : (size_t)m * sizeof(uint32_t);
+    DevBuf d_s, d_f, d_n, d_o;
+    if (int r = grow(c, d_s, sh_bytes, "probe coefficients")) return r;
+    if (int r = grow(c, d_f, first_bytes, "probe queries")) return r;
+    if (int r = grow(c, d_n, v_bytes, "probe queries")) return r;
+    if (int r = grow(c, d_o, v_bytes, "probe results")) return r;
+    HIPCHK(hipMemcpy(d_s.ptr, sh, sh_bytes, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_f.ptr, first, first_bytes, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_n.ptr, nrm, v_bytes, hipMemcpyHostToDevice));
+    const int e = grid ? cr::launch_probe_sample(*grid_of(grid), d_s.as<float>(), d_f.as<float>(), d_n.as<float>(),
+                                                 d_o.as<float>(), m, c->stream)
+                       : cr::launch_probe_eval(d_s.as<float>(), d_f.as<uint32_t>(), d_n.as<float>(), d_o.as<float>(), m,
+                                               c->stream);
+    if (e) return hip_fail(c, (hipError_t)e, "probe lookup kernel launch");
+    HIPCHK(hipMemcpyAsync(out, d_o.ptr, v_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return CR_OK;
+}
+int cr_probe_eval(cr_ctx *c, uint32_t n_probes, const float *sh, uint32_t m, const uint32_t *probe, const float *nrm,
+                  float *out) {
+    if (!c) return CR_E_INVALID;
+    if (const char *msg = cr::probe_check_eval(m, sh && probe && nrm && out, sh, n_probes, out))
+        return fail(c, CR_E_INVALID, msg);
+    for (uint32_t j = 0; j < m; j++)
+        if (probe[j] >= n_probes) return fail(c, CR_E_INVALID, "probe index outside the coefficients");
+    if (int rc = enter(c)) return rc;
+    if (m == 0) return CR_OK;
+    return probe_lookup_host(c, nullptr, n_probes, sh, m, probe, nrm, out);
+}
+int cr_probe_sample(cr_ctx *c, const cr_probe_grid *grid, const float *sh, uint32_t m, const float *pos,
+                    const float *nrm, float *out) {
+    if (!c) return CR_E_INVALID;
+    if (const char *msg = cr::probe_check_sample(grid_of(grid), m, sh && pos && nrm && out, sh, out))
+        return fail(c, CR_E_INVALID, msg);
+    if (int rc = enter(c)) return rc;
+    if (m == 0) return CR_OK;
+    return probe_lookup_host(c, grid, cr::probe_grid_count(*grid_of(grid)), sh, m, pos, nrm, out);
 }
 
 void cr_bake_params_default(cr_bake_params *out) {

@@ -82,6 +82,9 @@ struct cr_ctx : cr::CtxOptions { // (the options, cr_set_option's table: ctxopts
     crx::Event bake_ev;
     bool bake_pending = false;
     hipStream_t bake_stream = nullptr;
+    // SH probes (cr_probe_sh*), grow-only: the 27 (with moments 54) running sums per work item that a sample-chunked
+    // SH pass carries from chunk to chunk (probe.hip sum_samples_sh), where d_run / d_run2 have room for 3 each
+    crx::DevBuf d_probe_run;
     crx::DevBuf d_cull;      // camera-ray cull boxes, one per leaf reference (+ 4), per render
     crx::DevBuf d_cull_node; // ... their per-leaf unions, one per kd node
     cr_counters last{};
@@ -135,10 +138,12 @@ cr::BlendArgs blend_args(const cr_render_params *p, const float *gathered, float
 // m2 (MODE_BLEND): the layers' second moments are blended into this moment frame beside `out`
 // list (MODE_BLEND, nranks 1): a list pass -- the work items are the list_items entries of the device pixel list
 // (RenderArgs::list; a multiple of tile * tile, padded with skipped entries), not p's tiles
+// sh (a ray pass in sphere mode): an SH pass -- the paths' radiance is projected into sh->sh / sh->m2 [count][27] by
+// sum_samples_sh instead of summed into out / m2 (out is not written; run / run2 are bound here)
 int run_render(cr_ctx *c, const cr_camera *cam, const cr_render_params *p, float *out, int mode, hipStream_t st,
                uint32_t nl = 1, uint32_t piece_k = 0, uint32_t piece_m = 1, uint64_t stride = 0,
                float *m2 = nullptr, const uint32_t *list = nullptr, uint32_t list_items = 0,
-               const cr::RaySrc *rays = nullptr);
+               const cr::RaySrc *rays = nullptr, const cr::ShOut *sh = nullptr);
 // group.cpp: the communicator and buffers of the multi-process split (cr_destroy)
 void release_dist(cr_ctx *c);
 // The largest nl <= want (>= 1) whose paths fit one chunk when p's share (the frame for nranks 1, else rank

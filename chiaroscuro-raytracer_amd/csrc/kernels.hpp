@@ -485,8 +485,27 @@ int run_wavefront_lanes(const RenderArgs &A, WfLane *lanes, int nlanes, int num_
 struct RaySrc {
     const float *a, *b; // [count][3] each, device
     uint32_t id0;       // the stream id of entry 0
-    int gather;         // 1: a = positions, b = normals, the direction drawn about the normal
+    int gather;         // the mode.  0: (a, b) is the ray; 1: a = positions, b = normals, the direction drawn about
+                        // the normal; 2 (an SH pass): a = positions, b unused, the direction
+                        // drawn uniformly over the sphere (probe.hpp probe_dir; wf_camera_sphere)
 };
+enum { RAY_SRC_RAY = 0, RAY_SRC_GATHER = 1, RAY_SRC_SPHERE = 2 };
+// The outputs of an SH pass (cr_probe_sh_device; probe.hip sum_samples_sh, which takes the place of sum_samples):
+// entry e of the pass projects onto sh [count][27] (and m2, the moments, or null); run / run2 [n_items][27] carry the
+// chains across sample chunks (null when the pass is not chunked); id0 is RaySrc's.  An argument of that kernel
+// alone, as RaySrc is of generation 0.
+struct ShOut {
+    float *sh, *m2;
+    float *run, *run2;
+    uint32_t id0;
+};
+int launch_sum_samples_sh(const RenderArgs &A, bool first, bool last, const ShOut &H, hipStream_t st);
+// probe.hip: the lookups, a thread per query.  out [m][3] = the evaluation of probe probe[j]'s coefficients (sh
+// [..][27]) for normal nrm[j]; or of the coefficients interpolated at pos[j] in grid G
+struct ProbeGrid;
+int launch_probe_eval(const float *sh, const uint32_t *probe, const float *nrm, float *out, uint32_t m, hipStream_t st);
+int launch_probe_sample(const ProbeGrid &G, const float *sh, const float *pos, const float *nrm, float *out, uint32_t m,
+                        hipStream_t st);
 int launch_ray_list(uint32_t *list, uint32_t count, uint32_t n_items, hipStream_t st);
 int launch_wavefront_chunk(const RenderArgs &A, const WfArgs &W, int num_cus, hipStream_t st, const WfStreams &ss,
                            TraceEvents *te = nullptr, const RaySrc *rays = nullptr);

@@ -7,7 +7,9 @@
 // split by phase into kernels that exchange work through queues in HBM:
 //
 //   wf_camera                 one closest ray per path of the chunk (wf_camera_list: of a list pass;
-//                             wf_camera_rays: of a ray pass, whose first rays are the caller's)
+//                             wf_camera_rays: of a ray pass, whose first rays are the caller's;
+//                             wf_camera_sphere: of an SH pass, whose first rays leave the caller's points
+//                             in directions drawn over the sphere)
 //   wf_trace<closest>(1)
 //   for g = 1..K:
 //     wf_shade(g)             hit reconstruction, emission, NEE light sample
@@ -30,6 +32,7 @@
 // ChunkLauncher; the two chunk drivers differ in how they wait for the queue lengths and in their WfDriver policy.
 #include "append.hpp"
 #include "camcull.hpp"
+#include "probe.hpp"
 #include "raysort.hpp"
 #include "traverse.hpp"
 #include "wfgen.hpp"
@@ -288,6 +291,43 @@ __global__ void __launch_bounds__(256) wf_camera_rays(RenderArgs A, WfArgs W, Ra
             W.mark[p] = 0; // no resolve mark (wf_resolve)
             W.ray[1][2 * (size_t)p] = pk(o, p);
             W.ray[1][2 * (size_t)p + 1] = pk(d, 0u);
+        } else if (p < W.P) {
+            W.mark[p] = 0;
+            dead_entry(W.ray[1], p);
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) *cnt_closest(W, 1) = W.P;
+    flush_tallies(A, tl);
+}
+// The sphere flavour of wf_camera_rays (RaySrc mode 2; an SH pass): a = positions, b is not read,
+// and draws 0 and 1 aim the direction uniformly over the sphere (probe.hpp probe_dir, used as computed), so the path
+// continues with the counter at 2 as in gather mode.  A kernel of its own: a third value of the template's flag
+// would rename the two instantiations above.
+__global__ void __launch_bounds__(256) wf_camera_sphere(RenderArgs A, WfArgs W, RaySrc R) {
+    __shared__ unsigned long long tl[T_N];
+    if (threadIdx.x < T_N) tl[threadIdx.x] = 0;
+    __syncthreads();
+    for (uint32_t base = blockIdx.x * blockDim.x; base < W.P; base += gridDim.x * blockDim.x) {
+        const uint32_t p = base + threadIdx.x;
+        const uint32_t w = W.w0 + p;
+        uint32_t item = 0, s = 0, e = 0, ey = 0;
+        bool valid = p < W.P && w < A.n_work;
+        if (valid) {
+            item = w / A.s_count;
+            s = A.s0 + (w - item * A.s_count);
+            valid = item_pixel_of<true>(A, item, e, ey); // (a frame of n entries x 1: e is the entry)
+        }
+        tally(tl, T_PATHS, valid);
+        if (valid) {
+            Rng rng = path_rng(A, R.id0 + e, s);
+            const float *a = R.a + 3 * (size_t)e;
+            const uint32_t raw0 = rng_u32(rng), raw1 = rng_u32(rng);
+            float d[3];
+            probe_dir(raw0, raw1, d);
+            ctl_store(W, p, 1u, rng);
+            W.mark[p] = 0; // no resolve mark (wf_resolve)
+            W.ray[1][2 * (size_t)p] = pk(mk(a[0], a[1], a[2]), p);
+            W.ray[1][2 * (size_t)p + 1] = pk(mk(d[0], d[1], d[2]), 0u);
         } else if (p < W.P) {
             W.mark[p] = 0;
             dead_entry(W.ray[1], p);
@@ -1784,7 +1824,8 @@ struct ChunkLauncher {
         WfArgs &W = r.W;
         const WfStart s = wf_chunk_start(W, b->packet && !rays, A.eye_on_split != 0);
         W.cam_fused = s.cam_fused ? 1 : 0;
-        if (rays && rays->gather) hipLaunchKernelGGL(wf_camera_rays<true>, dim3(sgrid), dim3(256), 0, r.st, A, W, *rays);
+        if (rays && rays->gather == RAY_SRC_SPHERE) hipLaunchKernelGGL(wf_camera_sphere, dim3(sgrid), dim3(256), 0, r.st, A, W, *rays);
+        else if (rays && rays->gather) hipLaunchKernelGGL(wf_camera_rays<true>, dim3(sgrid), dim3(256), 0, r.st, A, W, *rays);
         else if (rays) hipLaunchKernelGGL(wf_camera_rays<false>, dim3(sgrid), dim3(256), 0, r.st, A, W, *rays);
         else if (s.camera) hipLaunchKernelGGL(A.list ? wf_camera_list : wf_camera, dim3(sgrid), dim3(256), 0, r.st, A, W);
         // (a ray pass never hands generation 1 to the tail, whose traversal has the build's leaf cull: first_rays)

@@ -388,6 +388,27 @@ int chiaro_raytracer_gather(chiaro_raytracer *r, const float *pos, const float *
         },
         CR_E_HIP);
 }
+int chiaro_raytracer_probes(chiaro_raytracer *r, const cr_probe_grid *grid, const float *pos, uint32_t n,
+                            uint32_t layers, float *sh_out) {
+    if (!r || layers < 1 || !sh_out || (!grid && n && !pos)) return CR_E_INVALID;
+    return guard(
+        [&]() -> int {
+            if (grid) r->r->bakeProbes(*grid, layers, sh_out);
+            else r->r->bakeProbes(pos, n, layers, sh_out);
+            return CR_OK;
+        },
+        CR_E_HIP);
+}
+int chiaro_raytracer_probes_sample(chiaro_raytracer *r, const cr_probe_grid *grid, const float *sh, const float *pos,
+                                   const float *nrm, uint32_t m, float *out) {
+    if (!r || !grid || (m && (!sh || !pos || !nrm || !out))) return CR_E_INVALID;
+    return guard(
+        [&]() -> int {
+            r->r->sampleProbes(*grid, sh, pos, nrm, m, out);
+            return CR_OK;
+        },
+        CR_E_HIP);
+}
 int chiaro_raytracer_bake(chiaro_raytracer *r, uint32_t width, uint32_t height, const float *uv, uint32_t layers,
                           uint32_t dilate, float *lightmap_out, float *dilated_out) {
     if (!r || !width || !height || layers < 1 || !lightmap_out) return CR_E_INVALID;

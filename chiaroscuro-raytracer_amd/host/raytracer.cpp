@@ -360,6 +360,28 @@ void RayTracer::gather(const float *pos, const float *nrm, uint32_t n, unsigned 
     cr_get_counters(ctx_, &counters_);
 }
 
+// bakeProbes() and sampleProbes(): cr_probe_sh of layers 1 .. layers with the Scene's sampling, and the grid lookup
+void RayTracer::bakeProbes(const float *pos, uint32_t n, unsigned layers, float *shOut) {
+    if (group_) throw std::runtime_error("chiaro: bakeProbes runs on one GPU (gpus 1)");
+    const cr_radiance_params p = radiance_params(scene);
+    if (cr_probe_sh(ctx_, n, pos, &p, layers, shOut, nullptr) != CR_OK)
+        throw std::runtime_error(std::string("chiaro: bakeProbes failed: ") + cr_last_error(ctx_));
+    cr_get_counters(ctx_, &counters_);
+}
+void RayTracer::bakeProbes(const cr_probe_grid &grid, unsigned layers, float *shOut) {
+    const uint64_t n = (uint64_t)grid.dims[0] * grid.dims[1] * grid.dims[2];
+    if (!n || n > 0xffffffffull) throw std::runtime_error("chiaro: bakeProbes: bad probe grid");
+    std::vector<float> pos(3 * (size_t)n);
+    if (cr_probe_grid_positions(&grid, pos.data()) != CR_OK) throw std::runtime_error("chiaro: bakeProbes: bad probe grid");
+    bakeProbes(pos.data(), (uint32_t)n, layers, shOut);
+}
+void RayTracer::sampleProbes(const cr_probe_grid &grid, const float *sh, const float *pos, const float *nrm, uint32_t m,
+                             float *out) {
+    if (group_) throw std::runtime_error("chiaro: sampleProbes runs on one GPU (gpus 1)");
+    if (cr_probe_sample(ctx_, &grid, sh, m, pos, nrm, out) != CR_OK)
+        throw std::runtime_error(std::string("chiaro: sampleProbes failed: ") + cr_last_error(ctx_));
+}
+
 // bakeLightmap(): cr_bake with the Scene's sampling; uv null: the grid atlas at the largest cell that fits
 static cr_bake_stats bake_with(cr_ctx *ctx, const Scene &scene, size_t n_tris, uint32_t W, uint32_t H, const float *uv,
                                unsigned layers, const cr_adaptive_params *ap, const cr_noise_params *np, unsigned dilate,

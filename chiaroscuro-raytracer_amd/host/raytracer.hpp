@@ -85,6 +85,17 @@ class RayTracer {
      * temporal history are untouched.  One GPU only. */
     void radiance(const float *orig, const float *dir, uint32_t n, unsigned layers, float *out);
     void gather(const float *pos, const float *nrm, uint32_t n, unsigned layers, float *out);
+    /* This build: SH irradiance probes (cr_probe_sh / cr_probe_sample, include/chiaro_hip.h "probes").  bakeProbes:
+     * the order-2 spherical-harmonic projection of the light arriving at n points (pos [n][3]), or at the probes of
+     * a grid in index order, shOut [n][27] = sh[i][k][c]; layers 1 .. layers of scene.samples samples with scene.k,
+     * scene.background and scene.seed, probe i on the stream of pixel index i.  sampleProbes: the mean incoming
+     * radiance under the cosine density (irradiance / pi, what gather returns) at m points (pos, nrm: [m][3]) from
+     * the coefficients of the grid's probes, trilinearly interpolated, with no visibility weighting; out [m][3].  The
+     * frame, the progressive state and the temporal history are untouched.  One GPU only. */
+    void bakeProbes(const float *pos, uint32_t n, unsigned layers, float *shOut);
+    void bakeProbes(const cr_probe_grid &grid, unsigned layers, float *shOut);
+    void sampleProbes(const cr_probe_grid &grid, const float *sh, const float *pos, const float *nrm, uint32_t m,
+                      float *out);
     /* This build: lightmap baking (cr_bake, include/chiaro_hip.h "lightmap baking").  The W x H lightmap over the
      * lightmap UVs uv ([triangles][6], the scene's triangle order): the mean incoming radiance under the cosine
      * density at the surface point under each covered texel's centre (times pi and the albedo: the caller's), texel

@@ -771,6 +771,81 @@ int cr_bake(cr_ctx *ctx, const cr_bake_params *p, const float *uv /* host, may b
             float *lightmap_out, float *m2_out, uint32_t *layers_out, uint32_t *owner_out, float *dilated_out,
             cr_bake_stats *stats_out);
 
+/* ------------------------------------------------------------ probes --
+ * SH IRRADIANCE PROBES: the light arriving at a point from every direction, path-traced along
+ * directions drawn uniformly over the sphere and projected onto the nine real spherical harmonics of order <= 2, per
+ * colour channel; and the lookups that turn such coefficients back into the quantity cr_gather returns -- the mean
+ * incoming radiance under the cosine density about a normal (irradiance / pi) -- at a probe or interpolated in a
+ * regular grid of probes.  What lights everything that has no lightmap.  The definition, bit for bit; csrc/probe.hpp
+ * is its C++ statement and tests/probe_model.py its numpy one.  Every step is one correctly rounded float32 operation
+ * unless marked double; nothing is contracted; every sum starts from +0 and adds its terms in the order given;
+ * max(0, v) is v > 0 ? v : 0.
+ *
+ * SPHERE DIRECTION.  Sample s of layer L of probe i draws from the render's stream (seed, L, id0 + i, s).  Draws 0 and
+ * 1 aim it -- the path continues with the counter at 2, as a cr_gather path does:
+ *     u0 = uniform(0, 1), u1 = uniform(0, 1)     (the render's: raw / 2^32, below 1, times (1 - 0) plus 0)
+ *     z = u0 * 2 + (-1),  r = sqrt(max(0, 1 - z*z))
+ *     phi = (float)((double)u1 * 6.283185307179586),  (sn, cs) = sinf(phi), cosf(phi) (the render's restatement)
+ *     d = (r*cs, r*sn, z)
+ * The density is 1 / (4 pi).  d is used as computed -- not renormalised -- as the ray direction and as the basis
+ * argument.  The ray starts at the probe's position.
+ *
+ * BASIS.  K0 = 0.28209479, K1 = 0.48860251, K2 = 1.0925484, K3 = 0.31539157, K4 = 0.54627422 (float32):
+ *     Y = [K0, K1*y, K1*z, K1*x, K2*(x*y), K2*(y*z), K3*(3*(z*z) - 1), K2*(x*z), K4*(x*x - y*y)]
+ *
+ * PROJECTION.  With r_s the radiance of sample s's path (what cr_radiance returns for that ray at spp 1), coefficient
+ * k and channel c of a layer are t = sum over s, in sample order, of p = Y_k(d_s) * r_s[c]; the layer is blended as a
+ * frame pixel is, (old*(L-1) + t*(1/spp)) / L (old not read for L == 1); the moment array takes q = sum of p*p the
+ * same way.  The stored value is the mean of Y L; the 4 pi of the density lives in the evaluation.  Layout
+ * sh[i][k][c]: 27 floats per probe, the moment array the same.
+ *
+ * EVALUATION for normal n (used as given):  A = [1, 2/3, 2/3, 2/3, 1/4, 1/4, 1/4, 1/4, 1/4] as float32,
+ *     e = sum over k = 0..8 of (A_k * Y_k(n)) * sh[k][c],   out[c] = max(0, 12.566371f * e)
+ *
+ * GRID.  Probe (x, y, z) of a cr_probe_grid has index (z*ny + y)*nx + x and sits at origin[a] + (float)i_a * step[a].
+ * A lookup at p works per axis a: with dims[a] == 1, i0 = i1 = 0 and t = 0; otherwise f = (p[a] - origin[a]) / step[a],
+ * clamped (f > 0 ? f : 0, then f < hi ? f : hi with hi = (float)(dims[a] - 1)), i0 = min((uint32_t)f, dims[a] - 2),
+ * t = f - (float)i0, i1 = i0 + 1.  A corner's weight is (wx*wy)*wz with w = 1 - t for the lower index and t for the
+ * upper; the interpolated coefficient is the sum of w * sh over the eight corners, in z, y, x order with x fastest;
+ * the evaluation follows.  A point outside the grid takes the nearest face's values.  No visibility or occlusion
+ * weighting: a probe behind a wall counts as one in front of it (out of scope).
+ *
+ * One GPU; "perf_counters" 1 is refused as for any ray pass.  The ctx's accumulators, adaptive lists, temporal history
+ * and bake buffers are untouched. */
+typedef struct cr_probe_grid {
+    float origin[3]; /* probe (0, 0, 0) */
+    float step[3];   /* finite and > 0 on every axis with dims > 1 (not read on the others) */
+    uint32_t dims[3];
+} cr_probe_grid;
+void cr_probe_struct_sizes(uint32_t *grid_bytes);
+/* pos_out [nx*ny*nz][3] (host) in index order.  Needs no device.  CR_E_INVALID: null, a dims of 0, more than
+ * 0xffffffff probes, a non-finite origin, a bad step. */
+int cr_probe_grid_positions(const cr_probe_grid *grid, float *pos_out);
+/* Layers p->layer .. + nlayers - 1 of the projection at n device points d_pos [n][3], blended onto d_sh [n][27] and,
+ * when given, d_m2 [n][27].  p as for cr_radiance_device (probe i is stream p->id0 + i).  Returns when complete.
+ * Errors (arguments, then the device, then the scene): CR_E_INVALID as cr_radiance_device, and for 27 * n floats
+ * overflowing a size; n == 0 is CR_OK with nothing launched. */
+int cr_probe_sh_device(cr_ctx *ctx, uint32_t n, const float *d_pos, const cr_radiance_params *p, uint32_t nlayers,
+                       float *d_sh, float *d_m2 /* may be null */, void *stream);
+/* ... on host arrays; sh / m2 are read for p->layer > 1 and written. */
+int cr_probe_sh(cr_ctx *ctx, uint32_t n, const float *pos, const cr_radiance_params *p, uint32_t nlayers, float *sh,
+                float *m2 /* may be null */);
+/* d_out[j] [m][3] = the evaluation of probe d_probe[j]'s coefficients for normal d_nrm[j].  The indices are the
+ * caller's: none is checked against the size of d_sh.  Needs no scene.  Stream-ordered.  CR_E_INVALID: a null array
+ * (m > 0), d_out aliasing d_sh. */
+int cr_probe_eval_device(cr_ctx *ctx, uint32_t m, const float *d_sh, const uint32_t *d_probe, const float *d_nrm,
+                         float *d_out, void *stream);
+/* d_out[j] [m][3] = the grid lookup at d_pos[j] for normal d_nrm[j] over d_sh [nx*ny*nz][27].  Needs no scene.
+ * Stream-ordered.  CR_E_INVALID: a bad grid (cr_probe_grid_positions'), a null array (m > 0), d_out overlapping
+ * d_sh. */
+int cr_probe_sample_device(cr_ctx *ctx, const cr_probe_grid *grid, const float *d_sh, uint32_t m, const float *d_pos,
+                           const float *d_nrm, float *d_out, void *stream);
+/* The host forms: sh holds n_probes probes (cr_probe_sample: the grid's), and an index >= n_probes is CR_E_INVALID. */
+int cr_probe_eval(cr_ctx *ctx, uint32_t n_probes, const float *sh, uint32_t m, const uint32_t *probe, const float *nrm,
+                  float *out);
+int cr_probe_sample(cr_ctx *ctx, const cr_probe_grid *grid, const float *sh, uint32_t m, const float *pos,
+                    const float *nrm, float *out);
+
 int cr_get_counters(cr_ctx *ctx, cr_counters *out);
 /* Device time (ms) of the last render kernel, HIP events on its own stream. */
 float cr_last_kernel_ms(cr_ctx *ctx);

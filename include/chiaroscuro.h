@@ -18,6 +18,9 @@
  *   chiaro_raytracer_radiance / _gather
  *                            RayTracer::sendRay (src/rayTracer.cpp:76-135) along caller rays (this build; cr_radiance,
  *                            cr_gather)
+ *   chiaro_raytracer_probes / _probes_sample
+ *                            order-2 SH irradiance probes and their grid lookup (this build; cr_probe_sh,
+ *                            cr_probe_sample)
  *   chiaro_raytracer_bake / _bake_adaptive
  *                            a lightmap of the scene in a second UV set (this build; cr_bake)
  *   chiaro_raytracer_raytrace_until / _noise / _noise_map
@@ -154,6 +157,18 @@ int chiaro_raytracer_radiance(chiaro_raytracer *r, const float *orig, const floa
                               float *out);
 int chiaro_raytracer_gather(chiaro_raytracer *r, const float *pos, const float *nrm, uint32_t n, uint32_t layers,
                             float *out);
+/* RayTracer::bakeProbes / RayTracer::sampleProbes (cr_probe_sh / cr_probe_sample, include/chiaro_hip.h "probes").
+ * _probes: the order-2 SH projection of the light arriving at the probes of `grid` in index order or, with grid null,
+ * at the n points pos [n][3]; sh_out [probes][27] = sh[i][k][c].  Layers 1 .. layers with the Scene's samples, k,
+ * background and seed; probe i draws from the stream of pixel index i.  _probes_sample: the mean incoming radiance
+ * under the cosine density (irradiance / pi, what _gather returns) at m points (pos, nrm: [m][3]) from the grid's
+ * coefficients sh, trilinearly interpolated, no visibility weighting; out [m][3].  The frame, the progressive state
+ * and the temporal history are untouched.  CR_E_INVALID for a null pointer or layers == 0; CR_E_HIP with
+ * chiaro_last_error otherwise.  One GPU only. */
+int chiaro_raytracer_probes(chiaro_raytracer *r, const cr_probe_grid *grid /* may be null */, const float *pos,
+                            uint32_t n, uint32_t layers, float *sh_out);
+int chiaro_raytracer_probes_sample(chiaro_raytracer *r, const cr_probe_grid *grid, const float *sh, const float *pos,
+                                   const float *nrm, uint32_t m, float *out);
 /* RayTracer::bakeLightmap (cr_bake, include/chiaro_hip.h "lightmap baking"): the width x height lightmap over the
  * lightmap UVs uv ([triangles][6] in the scene's triangle order; null: the grid atlas of the scene's triangles at the
  * largest cell that fits, gutter 0.25, in the map's top-left corner) -- the mean incoming radiance under the cosine
