@@ -2,9 +2,9 @@
  * oracle.c -- CPU restatement of Chiaroscuro's per-pixel render loop.
  *
  * TEST INFRASTRUCTURE ONLY (see oracle.h header for the rules and the parity
- * status: kd build / traversal / BRDF / integrator are parity unpinned by the
- * reference itself; texture lookup and glm arithmetic are pinned by
- * tests/golden/ref_*.json from oracle/ref).
+ * status: texture lookup, glm arithmetic, kd build, traversal, BRDF, the two
+ * distributions and the integrator are pinned by tests/golden/ref_* from
+ * oracle/ref, the reference's own sources compiled unmodified).
  *
  * Every function cites the reference line it restates.  Arithmetic is written
  * operation-for-operation in the order glm 0.9.8.5 / the reference evaluates it
@@ -66,12 +66,17 @@ static inline uint32_t rng_u32(rng_t *r) { uint32_t u = mix32(r->key + r->ctr * 
  * generate_canonical<float,24> (random.tcc:3348-3377) then * (b - a) + a. */
 static inline float rng_uniform(rng_t *r, float a, float b) {
     float c = (float)rng_u32(r) / 4294967296.0f;
+#ifndef OR_VARIANT_NO_CLAMP
     if (c >= 1.0f) c = 0x1.fffffep-1f; /* nextafter(1, 0) */
+#endif
     return c * (b - a) + a;
 }
 /* std::uniform_int_distribution<int>(0, n-1): libstdc++-11 Lemire path
  * (uniform_int_dist.h:245-269, 316) -- Scene::randomLight, src/scene.cpp:79-82 */
 static inline uint32_t rng_index(rng_t *r, uint32_t n) {
+#ifdef OR_VARIANT_INDEX_NO_DRAW_1
+    if (n == 1) return 0;
+#endif
     uint64_t prod = (uint64_t)rng_u32(r) * (uint64_t)n;
     uint32_t low = (uint32_t)prod;
     if (low < n) {
@@ -80,6 +85,21 @@ static inline uint32_t rng_index(rng_t *r, uint32_t n) {
     }
     return (uint32_t)(prod >> 32);
 }
+
+/* OR_VARIANT_*: deliberately WRONG readings of the reference, one per macro, never defined in a build that
+ * anything uses.  tests/test_oracle_golden.py compiles each into a scratch library and requires the
+ * reference-pinned fixtures to tell it from the reference (a fixture that cannot is missing the case):
+ *   OR_VARIANT_BELOW_LT           belowFirst's tie `dir <= 0` read as `dir < 0`
+ *   OR_VARIANT_SHADOW_LE          the shadow test's `t < tmax` read as `t <= tmax`
+ *   OR_VARIANT_CLOSEST_LE         the leaf loop's `dist < tmax` read as `dist <= tmax`
+ *   OR_VARIANT_JITTER_X_FIRST     the camera sample's x jitter drawn before the y jitter
+ *   OR_VARIANT_INDEX_NO_DRAW_1    no draw for a single light
+ *   OR_VARIANT_NO_CLAMP           generate_canonical's `>= 1` clamp left out */
+#ifdef OR_VARIANT_BELOW_LT
+#define OR_BELOW_TIE(da) ((da) < 0)
+#else
+#define OR_BELOW_TIE(da) ((da) <= 0)
+#endif
 
 /* ------------------------------------------------------------- sincos -- */
 /* glibc's sinf / cosf, which src/brdf.cpp:52-53 calls: glibc 2.35 x86-64 (FMA
@@ -492,7 +512,11 @@ static int node_closest(const or_scene *s, v3 o, v3 d, uint32_t *tri, float *bx,
             uint32_t t = s->refs[nd->first + j];
             float px, py, pd;
             CT_HOT(ct, OR_C_TRITEST);
+#ifdef OR_VARIANT_CLOSEST_LE
+            if (tri_test(s, o, d, t, &px, &py, &pd) && pd <= tmax) {
+#else
             if (tri_test(s, o, d, t, &px, &py, &pd) && pd < tmax) {
+#endif
                 *bx = px; *by = py; tmax = pd; *tri = t; ret = 1;
             }
         }
@@ -503,7 +527,7 @@ static int node_closest(const or_scene *s, v3 o, v3 d, uint32_t *tri, float *bx,
     const int a = (int)nd->axis;
     const float oa = comp(o, a), da = comp(d, a);
     const float tsplit = (nd->split - oa) / da;
-    const uint32_t below = (oa < nd->split) || (oa == nd->split && da <= 0);
+    const uint32_t below = (oa < nd->split) || (oa == nd->split && OR_BELOW_TIE(da));
     if (tsplit >= tmax || tsplit < 0)
         return node_closest(s, o, d, tri, bx, by, dist, nd->child + (1 - below), tmin, tmax, ct);
     else if (tsplit <= tmin)
@@ -538,7 +562,11 @@ static inline int shadow_tri(const or_scene *s, v3 o, v3 d, uint32_t t, float tm
     const float by = f * dot(d, q);
     if (by < 0.f || by + bx > 1.f) return 0;
     const float t_ = f * dot(e2, q);
+#ifdef OR_VARIANT_SHADOW_LE
+    return t_ >= 0.f && t_ <= tmax;
+#else
     return t_ >= 0.f && t_ < tmax;
+#endif
 }
 
 /* kdtree.cpp:322-344 */
@@ -560,7 +588,7 @@ static int node_shadow(const or_scene *s, v3 o, v3 d, uint32_t light, uint32_t n
     const int a = (int)nd->axis;
     const float oa = comp(o, a), da = comp(d, a);
     const float tsplit = (nd->split - oa) / da;
-    const uint32_t below = (oa < nd->split) || (oa == nd->split && da <= 0);
+    const uint32_t below = (oa < nd->split) || (oa == nd->split && OR_BELOW_TIE(da));
     if (tsplit >= tmax || tsplit < 0)
         return node_shadow(s, o, d, light, nd->child + (1 - below), tmin, tmax, ct);
     else if (tsplit <= tmin)
@@ -723,13 +751,19 @@ static inline v3 camera_sample(const float cam[12], uint32_t x, uint32_t y, rng_
     *eye = V3(cam[0], cam[1], cam[2]);
     const v3 lu = V3(cam[3], cam[4], cam[5]), dx = V3(cam[6], cam[7], cam[8]), dy = V3(cam[9], cam[10], cam[11]);
     /* rayTracer.cpp:61 -- g++ evaluates the y-jitter draw before the x-jitter */
+#ifdef OR_VARIANT_JITTER_X_FIRST
+    const float ux = rng_uniform(rng, 0.f, 1.f);
+    const float uy = rng_uniform(rng, 0.f, 1.f);
+#else
     const float uy = rng_uniform(rng, 0.f, 1.f);
     const float ux = rng_uniform(rng, 0.f, 1.f);
+#endif
     return add(add(lu, muls(dx, (float)x + ux)), muls(dy, (float)y + uy));
 }
 
-void or_path(or_scene *s, const float cam[12], uint32_t xres, uint32_t yres, int k, const float bg[3],
-             uint32_t seed, uint32_t layer, uint32_t x, uint32_t y, uint32_t sample, float out[3]) {
+void or_path_words(or_scene *s, const float cam[12], uint32_t xres, uint32_t yres, int k, const float bg[3],
+                   uint32_t seed, uint32_t layer, uint32_t x, uint32_t y, uint32_t sample, float out[3],
+                   uint32_t *words) {
     (void)yres;
     itg_t it = {s, k, V3(bg[0], bg[1], bg[2])};
     ctr_t ct; memset(&ct, 0, sizeof ct);
@@ -738,6 +772,11 @@ void or_path(or_scene *s, const float cam[12], uint32_t xres, uint32_t yres, int
     v3 dir = camera_sample(cam, x, y, &rng, &eye);
     v3 r = send_ray(&it, eye, dir, 1, &rng, &ct);
     out[0] = r.x; out[1] = r.y; out[2] = r.z;
+    if (words) *words = rng.ctr;
+}
+void or_path(or_scene *s, const float cam[12], uint32_t xres, uint32_t yres, int k, const float bg[3],
+             uint32_t seed, uint32_t layer, uint32_t x, uint32_t y, uint32_t sample, float out[3]) {
+    or_path_words(s, cam, xres, yres, k, bg, seed, layer, x, y, sample, out, NULL);
 }
 
 void or_rng_draws(uint32_t seed, uint32_t layer, uint32_t pixel, uint32_t sample, uint32_t n, uint32_t *out) {

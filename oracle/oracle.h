@@ -8,13 +8,17 @@
  *
  * Parity status (see DESIGN.md "Oracle"): the reference as shipped does not
  * build (src/prng.cpp and include/prng.hpp are missing; kdtree.cpp/rayTracer.cpp
- * need assimp/FreeImage headers absent from this image), so the traversal, kd
- * build, BRDF and integrator restated here are PARITY UNPINNED by the reference
- * itself.  The pieces that DO compile from the reference's own sources without
- * stand-ins -- Texture::getColorAt (src/mesh.cpp:21-35) and the vendored glm
- * 0.9.8.5 arithmetic used by rayTrace's camera (src/rayTracer.cpp:41-49) and by
- * normalize/cross/dot/distance -- are pinned against tests/golden/ref_*.json,
- * produced by oracle/ref (oracle/_ref build).
+ * need assimp/FreeImage headers absent from this image).  What is restated here
+ * is pinned against fixtures recorded from the reference's own sources compiled
+ * unmodified (oracle/ref, oracle/_ref build; tests/golden/ref_*):
+ *   - without stand-ins: Texture::getColorAt (src/mesh.cpp:21-35) and the
+ *     vendored glm 0.9.8.5 arithmetic of rayTrace's camera
+ *     (src/rayTracer.cpp:41-49) and of normalize/cross/dot/distance;
+ *   - through declaration-only stand-in headers (oracle/ref/standin): the kd
+ *     build, both traversals, Diffuse::sample_wi, libstdc++'s two
+ *     distributions as uniformFloat / Scene::randomLight call them, and
+ *     RayTracer::sendRay with its draw order (G1-G4, oracle/ref/ref_hot.cpp).
+ * Not pinned: the counter function of the RNG stream, which is ours.
  */
 #ifndef CHIARO_ORACLE_H
 #define CHIARO_ORACLE_H
@@ -88,6 +92,10 @@ void or_rng_index_kat(uint32_t key, uint32_t ctr, uint32_t n, uint32_t *out, uin
 /* Path KAT (G4): radiance of one camera sample, recursion exactly as sendRay. */
 void or_path(or_scene *s, const float cam[12], uint32_t xres, uint32_t yres, int k, const float bg[3],
              uint32_t seed, uint32_t layer, uint32_t x, uint32_t y, uint32_t sample, float out[3]);
+/* the same, and the number of raw draws the path consumed (jitter included) */
+void or_path_words(or_scene *s, const float cam[12], uint32_t xres, uint32_t yres, int k, const float bg[3],
+                   uint32_t seed, uint32_t layer, uint32_t x, uint32_t y, uint32_t sample, float out[3],
+                   uint32_t *words);
 
 /* Render rows [y0, y1) with row stride ystep of layer `layer`:
  *   pixels = (old * (L-1) + mean) / L   (src/rayTracer.cpp:64)

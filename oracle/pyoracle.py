@@ -65,6 +65,8 @@ def lib():
             "or_rng_index_kat": (None, [C.c_uint32, C.c_uint32, C.c_uint32, UP, UP]),
             "or_path": (None, [P, FP, C.c_uint32, C.c_uint32, C.c_int, FP, C.c_uint32, C.c_uint32, C.c_uint32,
                                C.c_uint32, C.c_uint32, FP]),
+            "or_path_words": (None, [P, FP, C.c_uint32, C.c_uint32, C.c_int, FP, C.c_uint32, C.c_uint32, C.c_uint32,
+                                     C.c_uint32, C.c_uint32, FP, UP]),
             "or_render": (None, [P, FP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, FP, C.c_uint32, C.c_uint32,
                                  C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, FP, C.POINTER(C.c_uint64)]),
             "or_render_pixels": (None, [P, FP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, FP, C.c_uint32,
@@ -181,6 +183,13 @@ class OracleScene:
         out = np.zeros(3, np.float32)
         lib().or_path(self.h, _p(_f(cam)), xres, yres, k, _p(_f(bg)), seed, layer, x, y, sample, _p(out))
         return out
+
+    def path_words(self, cam, xres, yres, k, bg, seed, layer, x, y, sample):
+        """path() and the number of raw draws the path consumed."""
+        out, words = np.zeros(3, np.float32), np.zeros(1, np.uint32)
+        lib().or_path_words(self.h, _p(_f(cam)), xres, yres, k, _p(_f(bg)), seed, layer, x, y, sample, _p(out),
+                            _p(words, C.c_uint32))
+        return out, int(words[0])
 
     def render(self, cam, xres, yres, spp, k, seed, layer=1, bg=(0, 0, 0), pixels=None, y0=0, y1=None, ystep=1,
                threads=0, lean=False):

@@ -11,8 +11,10 @@
 //     and light surface                            src/kdtree.cpp:72-77
 //   - the preview camera (src/camera.cpp, linked)  as OpenGLPreview drives it
 //     (src/openglPreview.cpp:12-15, 39, 178-195)
-// Nothing here is a stand-in for a missing header: every header it includes
-// ships in /root/reference/include.
+// Nothing in THIS file needs a stand-in for a missing header: every header it
+// includes ships with the reference.  The hot path (kd build, traversal, BRDF,
+// sendRay) is driven by ref_hot.cpp beside it, which does need the declaration-only
+// stand-ins of oracle/ref/standin.
 #include "camera.hpp"
 #include "mesh.hpp"
 

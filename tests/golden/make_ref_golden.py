@@ -11,6 +11,23 @@ and records its outputs on fixed inputs as JSON fixtures:
   ref_preview_camera.json  the preview camera (src/camera.cpp as OpenGLPreview drives
                     it) over scripted key / mouse / scroll sequences
 
+and, from the reference's own src/kdtree.cpp, src/brdf.cpp, src/scene.cpp and src/rayTracer.cpp compiled
+unmodified beside them (oracle/ref/ref_hot.cpp; stand-in headers for assimp, FreeImage and the missing prng.hpp
+under oracle/ref/standin), the fixtures tests/refpin.py reads:
+
+  ref_scene_<name>.npz  G1: the tree KDTree::KDTree builds (pre-order), padded root box, light list, with the soup
+  ref_rays_<name>.npz   G2: KDTree::intersectRay / intersectShadowRay over aimed rays
+  ref_brdf.npz          G3: Diffuse::sample_wi / f, uniformFloat through std::uniform_real_distribution,
+                        Scene::randomLight through std::uniform_int_distribution, on scripted words
+  ref_paths.npz         G4: RayTracer::sendRay per (pixel, sample): radiance and words consumed
+
+The scripted words are pyoracle.rng_draws' (the counter stream is this project's by definition; what is pinned
+is what libstdc++ and the reference make of the words).  G4 goes per path through hot_send_ray, which restates
+the one line of RayTracer::rayTrace that draws the jitter; as a self-check the reference's real rayTrace is run
+on the concatenation of the words each path consumed, for layers 1 and 2 of the Cornell case, and its `pixels`
+must equal the in-order float32 blend of the per-path radiances bit for bit (it does: glm 0.9.8.5 zero-initialises
+rayTrace's `glm::vec3 temp`).
+
 Floats are stored as their IEEE-754 bit patterns (uint32) so tests compare bitwise.
 Usage:  python tests/golden/make_ref_golden.py      (needs /root/reference)
 """
@@ -25,6 +42,7 @@ from pathlib import Path
 import numpy as np
 
 ROOT = Path(__file__).resolve().parents[2]
+sys.path[:0] = [str(Path(__file__).resolve().parent)]
 HARNESS = ROOT / "oracle" / "_ref" / "libref_harness.so"
 FP = C.POINTER(C.c_float)
 
@@ -139,6 +157,8 @@ def main() -> int:
                      "args": bits(args), "out": bits(out)})
     (ROOT / "tests" / "golden" / "ref_preview_camera.json").write_text(json.dumps({"sequences": seqs}, indent=0))
     print("wrote ref_texture.json, ref_glm.json, ref_preview_camera.json")
+    import make_ref_hot
+    make_ref_hot.main(L)
     return 0
 
 

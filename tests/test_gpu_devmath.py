@@ -132,6 +132,42 @@ def test_rng_index(harness, po):
     report("rng_index", dc.same_words(got, exp, float_cols=[]), rec, got, exp)
 
 
+def test_rng_distributions_match_reference_libstdcxx(harness, po):
+    """G3 (tests/golden/ref_brdf.npz, read by tests/refpin.py): rng_uniform against what libstdc++'s own uniform_real_distribution<float>
+    made of the same word in the reference's uniformFloat, and rng_index against Scene::randomLight through
+    uniform_int_distribution -- values and words consumed, n = 1 included.  The golden bits, not the oracle's."""
+    assert rng_pass1(harness, po), "the raw draws are not the CPU's on this GPU: rng_index is not launched"
+    import refpin
+    g = refpin.load_brdf()
+    rec = [[1, dc.unmix32(c["word"]), 0, 0, 0, 1, c["a"], c["b"]] for c in g["uniform"]]
+    rec += [[1, c["key"], 0, 0, 0, 2, c["n"], 0] for c in g["index"]]
+    raw, info = harness("rng", np.array(rec, np.uint32).reshape(-1), "rng_refpin")
+    got = raw.view(np.uint32).reshape(-1, 14)
+    nu = len(g["uniform"])
+    assert info["cases"] == len(rec) == len(got) and nu >= 400 and len(g["index"]) >= 256
+    exp_u = np.array([[c["out"], c["consumed"]] for c in g["uniform"]], np.uint32)
+    assert [int(w) for w in got[:nu, 1]] == [c["word"] for c in g["uniform"]]  # (the scripted word was the draw)
+    report("rng_uniform vs libstdc++", dc.same_words(got[:nu, 10:12], exp_u, float_cols=[0]), rec[:nu], got[:nu, 10:12],
+           exp_u)
+    exp_i = np.array([[c["index"], c["consumed"]] for c in g["index"]], np.uint32)
+    assert got[nu:, 1:9].tolist() == [c["words"][:8] for c in g["index"]]
+    report("rng_index vs libstdc++", dc.same_words(got[nu:, 12:14], exp_i, float_cols=[]), rec[nu:], got[nu:, 12:14],
+           exp_i)
+
+
+def test_brdf_matches_reference(harness):
+    """G3: sample_wi against the reference's own Diffuse::sample_wi (src/brdf.cpp) on the sx, sy its
+    uniformFloat(-1, 1) produced: wi and pdf bits."""
+    import refpin
+    g = refpin.load_brdf()["sample_wi"]
+    rec = np.array([c["n"] + [c["sx"], c["sy"]] for c in g], np.uint32)
+    exp = np.array([c["wi"] + [c["pdf"]] for c in g], np.uint32)
+    raw, info = harness("brdf", rec.reshape(-1), "brdf_refpin")
+    got = raw.view(np.uint32).reshape(-1, 9)
+    assert info["cases"] == len(rec) == len(got) >= 1500
+    report("sample_wi vs the reference", dc.same_words(got[:, 5:9], exp), rec, got[:, 5:9], exp)
+
+
 def test_minmax(harness):
     rec, exp = dc.minmax_cases()
     raw, info = harness("minmax", rec.reshape(-1))

@@ -1,8 +1,10 @@
 """Pin the oracle against golden vectors produced by the reference's own code.
 
-tests/golden/ref_*.json come from oracle/_ref (tests/golden/make_ref_golden.py):
-the reference's src/mesh.cpp (Texture::getColorAt) and its vendored glm 0.9.8.5
-compiled unmodified.  Everything is compared bit for bit.
+tests/golden/ref_* come from oracle/_ref (tests/golden/make_ref_golden.py): the
+reference's src/mesh.cpp (Texture::getColorAt), src/camera.cpp, its vendored glm
+0.9.8.5 and -- G1-G4, read through tests/refpin.py -- its src/kdtree.cpp,
+src/brdf.cpp, src/scene.cpp and src/rayTracer.cpp, all compiled unmodified.
+Everything is compared bit for bit (a NaN on both sides counts as equal).
 """
 import json
 import os
@@ -92,10 +94,11 @@ def test_goldens_are_current():
     """Re-running the generator reproduces the committed fixtures (build container only)."""
     import subprocess
     import sys
-    before = {p.name: p.read_bytes() for p in GOLD.glob("ref_*.json")}
+    before = {p.name: p.read_bytes() for p in GOLD.glob("ref_*")}
+    assert sum(n.endswith(".npz") for n in before) >= 20 and sum(n.endswith(".json") for n in before) >= 3
     subprocess.run([sys.executable, str(GOLD / "make_ref_golden.py")], check=True, capture_output=True)
-    after = {p.name: p.read_bytes() for p in GOLD.glob("ref_*.json")}
-    assert before == after
+    after = {p.name: p.read_bytes() for p in GOLD.glob("ref_*")}
+    assert before.keys() == after.keys() and before == after
 
 
 def test_sincos_restatement_equals_host_libm(po):
@@ -147,3 +150,137 @@ def test_lean_oracle_is_the_same_render(po, ca):
     for key in ("closest", "shadow", "paths"):
         assert ca_[key] == cb[key] > 0
     assert ca_["tritest"] > 0 and cb["tritest"] == cb["inner"] == cb["leaf"] == 0
+
+
+# ------------------------------------------------------------------------------------------------
+# G1-G4: the kd build, both traversals, the BRDF and distributions, and sendRay, against what the
+# reference's own compiled objects gave (tests/refpin.py reads the fixtures; nothing here needs the
+# reference).
+import refpin  # noqa: E402
+
+
+def test_fixture_files_fit_the_size_limit():
+    files = sorted(GOLD.glob("ref_*"))
+    assert {p.name for p in files} >= ({"ref_scene_%s.npz" % n for n in refpin.SCENES} |
+                                       {"ref_rays_%s.npz" % n for n in refpin.SCENES} |
+                                       {"ref_brdf.npz", "ref_paths.npz"})
+    assert all(p.stat().st_size < 1000000 for p in files), [(p.name, p.stat().st_size) for p in files]
+
+
+def test_g1_oracle_kd_build_matches_reference(po):
+    """The tree KDTree::KDTree builds (src/kdtree.cpp:34-194) in pre-order, the padded root box and the light
+    list: the oracle's build, serial and threaded."""
+    res = refpin.oracle_tree_cases(po)
+    assert len(res) == 2 * len(refpin.SCENES)
+    assert all(not bad for bad in res.values()), {k: v for k, v in res.items() if v}
+    # the cases the scenes exist for
+    t = {n: refpin.GoldenScene(n) for n in refpin.SCENES}
+    assert len(t["ident24"].tree["is_leaf"]) == 1 and t["ident24"].tree["count"][0] == 24 > t["ident24"].leaf_size
+    assert (f32(t["negative"].box[3:]) < 0.00011).all() and (f32(t["negative"].box[3:]) > 0).all()  # FLT_MIN + pad
+    assert len({len(t[n].tree["is_leaf"]) for n in ("cornell_l1", "cornell_l8")}) == 2
+    assert len(t["nolight"].light_ids) == 0 and len(t["cornell_l8"].light_ids) == 2
+
+
+@pytest.mark.parametrize("threads", [1, 4])
+@pytest.mark.parametrize("name", refpin.SCENES)
+def test_g1_host_kd_build_matches_reference(ca, scenes, tmp_path, name, threads):
+    """The product's host build (host/kdtree.cpp; serial, and the OpenMP-task build) of the same triangles,
+    loaded from OBJ as the product loads any scene."""
+    gs = refpin.GoldenScene(name)
+    ld = refpin.Loaded(ca, scenes, tmp_path, gs)
+    e = ca.KDTree(ld.model, ld.scene, threads=threads).export()
+    assert refpin.tree_differences(refpin.preorder(e), gs, e["box"]) == []
+
+
+def test_g2_oracle_traversal_matches_reference(po):
+    """KDTree::intersectRay / intersectShadowRay (src/kdtree.cpp:196-344): slab test, descent with its belowFirst
+    ties and tsplit windows, both Moller-Trumbore variants."""
+    res = refpin.oracle_ray_cases(po)
+    assert res["n"] > 9 * 8000
+    assert res["closest"] == 0 and res["shadow"] == 0, res
+
+
+def test_g2_fixture_covers_its_ray_classes():
+    for name in refpin.SCENES:
+        r = refpin.load_rays(name)
+        have = set(np.unique(r["cls"]).tolist())
+        need = set(range(len(refpin.RAY_CLASSES)))
+        if name == "ident24":
+            need -= {refpin.RAY_CLASSES.index("on_split")}  # (a single leaf: no split plane)
+        if name not in ("ident24", "onplane", "torture_mini"):
+            need -= {refpin.RAY_CLASSES.index("equal_t")}  # (no coincident triangles)
+        sneed = set(range(len(refpin.SHADOW_CLASSES)))
+        if name != "torture_mini":  # (tests/torture.py's aimed rays need its room)
+            need -= {refpin.RAY_CLASSES.index("torture")}
+            sneed -= {refpin.SHADOW_CLASSES.index("torture")}
+        assert have == need, (name, have, need)
+        assert set(np.unique(r["scls"]).tolist()) == sneed, name
+        at, own = r["scls"] == 1, r["scls"] == 4
+        assert r["occ"][r["scls"] == 3].sum() > r["occ"][at].sum(), name  # t < tmax is strict
+        assert r["occ"][own].sum() <= r["occ"][at].sum(), name
+
+
+def test_g3_oracle_brdf_and_distributions_match_reference(po):
+    """Diffuse::sample_wi / f (src/brdf.cpp), uniformFloat through libstdc++'s uniform_real_distribution<float>
+    and Scene::randomLight through its uniform_int_distribution, with the words each consumed."""
+    res = refpin.oracle_brdf_cases(po)
+    assert res["n"] > 2000
+    assert (res["sample_wi"], res["uniform"], res["index"]) == (0, 0, 0), res
+    g = refpin.load_brdf()
+    one = [c for c in g["index"] if c["n"] == 1]
+    assert one and all(c["consumed"] == 1 and c["index"] == 0 for c in one)  # one light still draws
+    assert any(c["consumed"] > 1 for c in g["index"] if c["n"] == 3 and c["words"][0] == 0)
+    assert any(c["sx"] == 0 and c["sy"] == 0 for c in g["sample_wi"])
+
+
+def test_g4_oracle_paths_match_reference(po):
+    """RayTracer::sendRay (src/rayTracer.cpp:76-135) per (pixel, sample): radiance and words consumed."""
+    res = refpin.oracle_path_cases(po)
+    assert res["n"] == 2048 + 192 + 128 + 128
+    assert res["radiance"] == 0 and res["words"] == 0, res
+
+
+VARIANTS = {  # -D of oracle.c -> the fixtures that must tell it from the reference
+    "OR_VARIANT_BELOW_LT": ("rays", ("closest", "shadow")),
+    "OR_VARIANT_SHADOW_LE": ("rays", ("shadow",)),
+    "OR_VARIANT_CLOSEST_LE": ("rays", ("closest",)),
+    "OR_VARIANT_JITTER_X_FIRST": ("paths", ("radiance",)),
+    "OR_VARIANT_INDEX_NO_DRAW_1": ("brdf", ("index",)),
+    "OR_VARIANT_NO_CLAMP": ("brdf", ("uniform",)),
+}
+
+
+@pytest.mark.parametrize("variant", sorted(VARIANTS))
+def test_fixtures_catch_wrong_reading(tmp_path, variant):
+    """Must-fail builds: oracle.c with one deliberately wrong reading of the reference each, in a scratch
+    directory.  The fixtures must differ from it on at least one case; a variant that passes means the fixture
+    lacks the case that matters."""
+    import re
+    import subprocess
+    import sys
+    root = GOLD.parents[1]
+    mk = (root / "oracle" / "Makefile").read_text()
+    cflags = re.search(r"^CFLAGS\s*:=\s*(.*)$", mk, re.M).group(1).split()
+    subprocess.run(["gcc", *cflags, "-D" + variant, "-shared", "-o", str(tmp_path / "liboracle.so"),
+                    str(root / "oracle" / "oracle.c"), "-lm"], check=True, capture_output=True)
+    what, keys = VARIANTS[variant]
+    r = subprocess.run([sys.executable, str(GOLD.parent / "refpin.py"), what], capture_output=True, text=True,
+                       env={**os.environ, "CHIARO_ORACLE_DIR": str(tmp_path)}, check=True)
+    res = json.loads(r.stdout.strip().splitlines()[-1])
+    for k in keys:
+        assert res[k] > 0, (variant, res)
+
+
+def test_g4_blend_of_reference_paths_is_the_oracle_frame(po, ca):
+    """What tests/test_gpu_refpin.py holds cr_render to -- refpin.blend_frames over the reference's per-sample
+    radiances, through the camera the product computes for the fixture's view -- is the oracle's own or_render
+    of the same frames, layer by layer: the blend helper and the stored camera are sound without a GPU."""
+    for case, c in refpin.load_paths().items():
+        gs = refpin.GoldenScene(refpin.PATH_CASES[case])
+        cam = ca.camera(*(gs.view[i: i + 3].tolist() for i in (0, 3, 6)), float(gs.view[9]), c["xres"], c["yres"])
+        assert np.array_equal(cam.as_array().view(np.uint32), c["cam"].view(np.uint32)), case
+        osc, pix = gs.oracle(po), None
+        for li, frame in enumerate(refpin.blend_frames(c)):
+            pix, _ = osc.render(c["cam"], c["xres"], c["yres"], c["spp"], c["k"], c["seed"], layer=li + 1,
+                                bg=tuple(c["bg"].tolist()), pixels=pix, threads=2)
+            assert not refpin.same_bits(pix, frame).any(), (case, li + 1)
